@@ -7,11 +7,17 @@ HBM-resident before timing.  One step = one request: for each of the GPU's shard
 segment (fused gfx950 kernel), postCollection + buildAggregation (top-k on the host or GPU, winners' rows compacted on
 the GPU), then the coordinator reduce (RCCL across ranks when N > 1).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line.  value = docs aggregated per second for the whole job, with `--inflight` requests in
-flight (default 2: one request's builds and reduce overlap the next one's collects).  ms_per_request_latency: one request
+flight (default 2: one request's builds and reduce overlap the next one's collects); ms_per_step = the milliseconds one
+of the K timed steps took.  A plain run sets up, warms up, times the K steps and prints that line.
+`--dump-outputs DIR` also writes the last timed request's reduced result to DIR as float64 .npy arrays (dump_outputs
+below; the synthetic data is seeded, so two builds can be compared array for array).
+
+`--full` adds the phases below after the timed steps (and the self-check of the result), each in a run of its own,
+and their fields to the line.  ms_per_request_latency: one request
 at a time, its shards collected back to back (one plan and HIP stream per shard) and built on worker threads, as
 Elasticsearch runs one SEARCH thread per shard.  ms_per_step_sequential: nothing overlapping at all (one plan, collect
 -> build per shard, then the reduce); the collect kernels' HIP-event times come from that phase.
@@ -163,6 +169,46 @@ def self_check(workload, res, docs_total, matching=None):
     return not errs, errs
 
 
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this many bytes of arrays
+
+
+def dump_outputs(directory, tree):
+    """The reduced result a caller of the timed path receives (its parsed tree), as one float64 array per value path:
+    `hosts.buckets.per_hour.buckets.rt.sum.npy` holds every hour bucket's sum in the order of the response (terms in
+    result order, hours inside each term), `hosts.buckets.doc_count.npy` the terms' doc counts.  Counts are integers
+    below 2^53 (exact in a double), a missing value (null) is NaN, and a string (a term, a formatted date) is written
+    as its CRC-32 under `<path>.crc32`.  If the arrays exceed DUMP_BYTES, the long ones are cut to a fixed seeded sample
+    of their positions (in order; the same positions for arrays of one length, and the same from run to run)."""
+    import re
+    import zlib
+    import numpy as np
+    cols = {}
+
+    def walk(node, path):
+        if isinstance(node, dict):
+            for k, v in node.items():
+                walk(v, f"{path}.{k}" if path else k)
+        elif isinstance(node, list):
+            for v in node:
+                walk(v, path)
+        elif isinstance(node, str):
+            cols.setdefault(path + ".crc32", []).append(float(zlib.crc32(node.encode("utf-8"))))
+        else:
+            cols.setdefault(path, []).append(float("nan") if node is None else float(node))
+
+    walk(tree, "")
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in cols.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BYTES:
+        budget = max(DUMP_BYTES // 8 // len(arrays), 1)
+        for k, a in arrays.items():
+            if len(a) > budget:  # (seeded by the length: arrays of one level keep the same positions)
+                keep = np.random.default_rng([0x5EEDE1A5, len(a)]).choice(len(a), budget, replace=False)
+                arrays[k] = a[np.sort(keep)]
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, re.sub(r"[^A-Za-z0-9_.@-]", "_", k) + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -174,7 +220,14 @@ def main():
                          "scaling; S > 0 fixes the job's size: strong scaling, e.g. --shards 8 --docs 125000000 is "
                          "BASELINE configs 3-5's 1B docs in 8 shards)")
     ap.add_argument("--workload", default="north_star", choices=sorted(WORKLOADS))
-    ap.add_argument("--cpu-docs", type=int, default=640_000_000, help="CPU baseline sample size (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the headline figure: the request "
+                         "latency and the sequential step, the collect kernel's roofline, the first-request cost of a "
+                         "segment's cached products, the CPU baseline and the self-check of the result")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result of the last timed request to DIR as one float64 <name>.npy per value path of "
+                         "the reduced aggregation tree (rank 0)")
+    ap.add_argument("--cpu-docs", type=int, default=640_000_000, help="CPU baseline sample size (0 = skip; --full only)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="host threads of the CPU baseline, one shard each (0 = every CPU this job is allotted: its "
                          "affinity, capped by OMP_NUM_THREADS)")
@@ -193,6 +246,8 @@ def main():
     ap.add_argument("--traffic", default=os.path.join(HERE, "profiles", "hbm_traffic.json"),
                     help="PMC-derived HBM bytes per collect launch (profiles/), if measured for this workload")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -394,8 +449,30 @@ def main():
             el = float(t.item())
         return el
 
+    def shutdown():
+        builders.shutdown()
+        reducer.shutdown()
+        for st in sets:
+            for p in st:
+                p.close()
+        for seg in segs:
+            seg.close()
+        if comm:
+            comm.close()
+        engine.close()
+        if dist:
+            dist.destroy_process_group()
+
     precomputed = None
-    if args.workload == "config3" and per_gpu > 1:
+    if not args.full:
+        # a segment's cached products (compact columns, hot/cold statistics, encodeHash words) are built on its first
+        # collect: one untimed request per segment builds them, as the measured passes of --full below do
+        p = sets[0][0]
+        for seg in segs:
+            p.reset()
+            p.collect(seg)
+            p.build()
+    elif args.workload == "config3" and per_gpu > 1:
         # the per-segment statistics of the 10M-ordinal column (hot set, recoded column, cold postings: built on a
         # segment's first request and cached with it, as Elasticsearch caches global ordinals) -- their build time and
         # HBM footprint, measured on this GPU's segments 1.. (segment 0's first collect also allocates the plan's grid)
@@ -452,6 +529,40 @@ def main():
     pipelined = {"inline": run_inline, "rotate": run_rotate}.get(args.scheme, run)
     pipelined(args.warmup, inflight)
     elapsed = timed(pipelined, args.steps, inflight)
+    ms_per_step = elapsed * 1000.0 / args.steps
+    docs_total = args.docs * shards
+    value = docs_total / (elapsed / args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, final.to_dict())
+    out = {
+        "metric": "docs aggregated/sec (node) + achieved HBM GB/s, terms+date_histogram, 1B docs",
+        "value": value,
+        "unit": "docs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "inflight_requests": inflight,
+        "scheme": args.scheme,
+        "higher_is_better": True,
+        "scaling": "strong" if args.shards > 0 else "weak",
+        "vs_baseline": None,
+        "dtype": "int64/f64",
+        "data": "synthetic (deterministic splitmix64 log docs generated in HBM, seed 0x5EEDE1A5, shard = global shard id)",
+        "config": {"workload": args.workload, "request": desc, "docs_per_shard": args.docs, "shards": shards,
+                   "shards_per_gpu": per_gpu, "docs_total": docs_total,
+                   "collect": ("merged (one plan per GPU)" if merged else "per shard") +
+                              (", reduce across ranks through esgpu_comm_build_reduce" if xr else
+                               ", co-located reduce (esgpu_plans_build_reduce)" if colo else ""),
+                   "parallelism": f"{per_gpu} shard(s) per GPU x{world}"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        shutdown()
+        return
+
+    # --full: everything beside the headline figure
     elapsed_latency = timed(run, args.steps, 1) if inflight > 1 else elapsed
     for k in host_ms:  # host times per request, from the serial phase
         host_ms[k] = 0.0
@@ -479,13 +590,10 @@ def main():
             t = torch.tensor([matching], dtype=torch.int64, device=f"cuda:{local_rank}")
             dist.all_reduce(t)
             matching = int(t.item())
-    docs_total = args.docs * shards
     # (the device-resident reduce across ranks leaves the result on rank 0 only: the other ranks check nothing)
     checked, check_errors = (self_check(args.workload, final.to_dict(), docs_total, matching) if not xr or rank == 0
                              else (True, []))
 
-    ms_per_step = elapsed * 1000.0 / args.steps
-    value = docs_total / (elapsed / args.steps)
     avg_kernel_ms = kernel_ms[0] / args.steps
     bytes_per_step = kernel_bytes[0] // args.steps
     achieved = bytes_per_step / (avg_kernel_ms / 1000.0) / 1e9
@@ -512,29 +620,9 @@ def main():
         if world == 1 and args.cpu_docs > 0:
             threads = args.cpu_threads if args.cpu_threads > 0 else host_threads()
             cpu = cpu_baseline(args.workload, shards, args.cpu_docs, threads, args.cpu_single_docs)
-        out = {
-            "metric": "docs aggregated/sec (node) + achieved HBM GB/s, terms+date_histogram, 1B docs",
-            "value": value,
-            "unit": "docs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "inflight_requests": inflight,
-            "scheme": args.scheme,
+        out.update({
             "ms_per_request_latency": elapsed_latency * 1000.0 / args.steps,
             "ms_per_step_sequential": elapsed_seq * 1000.0 / args.steps,
-            "higher_is_better": True,
-            "scaling": "strong" if args.shards > 0 else "weak",
-            "vs_baseline": None,
-            "dtype": "int64/f64",
-            "data": "synthetic (deterministic splitmix64 log docs generated in HBM, seed 0x5EEDE1A5, shard = global shard id)",
-            "config": {"workload": args.workload, "request": desc, "docs_per_shard": args.docs, "shards": shards,
-                       "shards_per_gpu": per_gpu, "docs_total": docs_total,
-                       "collect": ("merged (one plan per GPU)" if merged else "per shard") +
-                                  (", reduce across ranks through esgpu_comm_build_reduce" if xr else
-                                   ", co-located reduce (esgpu_plans_build_reduce)" if colo else ""),
-                       "parallelism": f"{per_gpu} shard(s) per GPU x{world}"},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
                          "frac": achieved / PEAK_HBM_GBS, "traffic": traffic,
                          # two figures: frac_physical = the bytes the GPU layout must move (compact columns,
@@ -556,20 +644,9 @@ def main():
             "cpu_baseline": cpu,
             "checked": checked,
             "check_errors": check_errors[:5],
-        }
+        })
         print(json.dumps(out), flush=True)
-    builders.shutdown()
-    reducer.shutdown()
-    for st in sets:
-        for p in st:
-            p.close()
-    for seg in segs:
-        seg.close()
-    if comm:
-        comm.close()
-    engine.close()
-    if dist:
-        dist.destroy_process_group()
+    shutdown()
 
 
 if __name__ == "__main__":

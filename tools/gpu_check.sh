@@ -25,7 +25,7 @@ for s in $STEPS; do
     case $s in
         tests) run pytest_gpu 1100 python3 -u -m pytest "$R/tests" -m gpu -x -v -p no:cacheprovider --timeout 300 --timeout-method thread ;;
         kbench) run kbench 600 python3 "$R/tools/kbench.py" --docs 1000000000 --reps 5 ${KBENCH_ONLY:+--only $KBENCH_ONLY} ;;
-        bench) run bench 600 python3 "$R/bench.py" ;;
+        bench) run bench 600 python3 "$R/bench.py" --full ;;
         jitter) for j in 0 60000 3600000; do
                     run "kbench_jitter_$j" 300 python3 "$R/tools/kbench.py" --docs 1000000000 --reps 5 --ts-jitter $j \
                         --only north_star,config2_dh_ext,date_hist,terms_dh || exit 1
@@ -33,26 +33,26 @@ for s in $STEPS; do
         export) run export_bench 300 python3 "$R/tools/export_bench.py" --docs 250000000 --reps 3 ;;
         shape125) run kbench_125m 300 python3 "$R/tools/kbench.py" --docs 125000000 --reps 5 --shards 8 ;;
         configs) # every BASELINE config at its own shape (1 GPU: the 8 shards of configs 3-5 collected in turn)
-              run bench_config2 300 python3 "$R/bench.py" --workload config2 --docs 100000000 --cpu-docs 160000000 &&
-              run bench_config3 300 python3 "$R/bench.py" --workload config3 --shards 8 --docs 125000000 --cpu-docs 320000000 &&
-              run bench_config4 300 python3 "$R/bench.py" --workload config4 --shards 8 --docs 125000000 --cpu-docs 320000000 &&
-              run bench_config5 300 python3 "$R/bench.py" --workload config5 --shards 8 --docs 125000000 --cpu-docs 320000000 &&
-              run bench_ns_shards8 300 python3 "$R/bench.py" --shards 8 --docs 125000000 --cpu-docs 0 ;;
+              run bench_config2 300 python3 "$R/bench.py" --full --workload config2 --docs 100000000 --cpu-docs 160000000 &&
+              run bench_config3 300 python3 "$R/bench.py" --full --workload config3 --shards 8 --docs 125000000 --cpu-docs 320000000 &&
+              run bench_config4 300 python3 "$R/bench.py" --full --workload config4 --shards 8 --docs 125000000 --cpu-docs 320000000 &&
+              run bench_config5 300 python3 "$R/bench.py" --full --workload config5 --shards 8 --docs 125000000 --cpu-docs 320000000 &&
+              run bench_ns_shards8 300 python3 "$R/bench.py" --full --shards 8 --docs 125000000 --cpu-docs 0 ;;
         coloab) # co-located reduce (one build_reduce call per request) vs one build per shard + host reduce (--no-colo)
               for i in 1 2; do for c in "" "--no-colo"; do
                   t=${c:+_nocolo}
-                  run "bench_ns8${t}_$i" 300 python3 "$R/bench.py" --shards 8 --docs 125000000 --cpu-docs 0 $c || exit 1
-                  run "bench_c5${t}_$i" 300 python3 "$R/bench.py" --workload config5 --shards 8 --docs 125000000 --cpu-docs 0 $c || exit 1
+                  run "bench_ns8${t}_$i" 300 python3 "$R/bench.py" --full --shards 8 --docs 125000000 --cpu-docs 0 $c || exit 1
+                  run "bench_c5${t}_$i" 300 python3 "$R/bench.py" --full --workload config5 --shards 8 --docs 125000000 --cpu-docs 0 $c || exit 1
               done; done ;;
         colotrace) # per-phase host marks of build_reduce (and each skeleton build) in the 8-shard north star / config 5
-              ESGPU_TRACE_BUILD=1 run bench_ns8_colotrace 300 python3 "$R/bench.py" --shards 8 --docs 125000000 --cpu-docs 0 \
+              ESGPU_TRACE_BUILD=1 run bench_ns8_colotrace 300 python3 "$R/bench.py" --full --shards 8 --docs 125000000 --cpu-docs 0 \
                   --steps 4 --warmup 2 &&
-              run bench_ns8 300 python3 "$R/bench.py" --shards 8 --docs 125000000 --cpu-docs 0 &&
-              run bench_c5 300 python3 "$R/bench.py" --workload config5 --shards 8 --docs 125000000 --cpu-docs 0 ;;
+              run bench_ns8 300 python3 "$R/bench.py" --full --shards 8 --docs 125000000 --cpu-docs 0 &&
+              run bench_c5 300 python3 "$R/bench.py" --full --workload config5 --shards 8 --docs 125000000 --cpu-docs 0 ;;
         schemes) # pipelined-phase A/B on one box: rotating plans vs one plan per shard
               for i in 1 2; do for sc in rotate sets; do
-                  run "bench_ns8_${sc}_$i" 300 python3 "$R/bench.py" --shards 8 --docs 125000000 --cpu-docs 0 --scheme $sc || exit 1
-                  run "bench_c5_${sc}_$i" 300 python3 "$R/bench.py" --workload config5 --shards 8 --docs 125000000 --cpu-docs 0 --scheme $sc || exit 1
+                  run "bench_ns8_${sc}_$i" 300 python3 "$R/bench.py" --full --shards 8 --docs 125000000 --cpu-docs 0 --scheme $sc || exit 1
+                  run "bench_c5_${sc}_$i" 300 python3 "$R/bench.py" --full --workload config5 --shards 8 --docs 125000000 --cpu-docs 0 --scheme $sc || exit 1
               done; done ;;
         dynab) # collect kernel: static block ranges vs dynamic chunk claiming (ESGPU_DYN), 125M- and 1B-doc shards
               for i in 1 2; do for d in 0 1; do
@@ -99,14 +99,14 @@ for s in $STEPS; do
         testsdyn) ESGPU_DYN=1 run pytest_gpu_dyn 1100 python3 -u -m pytest "$R/tests" -m gpu -x -v -p no:cacheprovider \
                       --timeout 300 --timeout-method thread ;;
         buildtrace) # per-phase host marks of every shard build (ESGPU_TRACE_BUILD) in the 8-shard north star
-              ESGPU_TRACE_BUILD=1 run bench_ns8_trace 300 python3 "$R/bench.py" --shards 8 --docs 125000000 --cpu-docs 0 \
+              ESGPU_TRACE_BUILD=1 run bench_ns8_trace 300 python3 "$R/bench.py" --full --shards 8 --docs 125000000 --cpu-docs 0 \
                   --steps 4 --warmup 2 ;;
         prof) cd /tmp && run rocprof_stats 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o bench -- \
-                  python3 "$R/bench.py" --steps 10 --warmup 3 --cpu-docs 0 --inflight 1 ;;
+                  python3 "$R/bench.py" --full --steps 10 --warmup 3 --cpu-docs 0 --inflight 1 ;;
         c3) # config 3 at 125M docs: clean (postings form) and with 1 % deletions (scatter form), kernel and bench line
               run kbench_c3_125m 300 python3 "$R/tools/kbench.py" --docs 125000000 --reps 5 --only config3_url &&
               run kbench_c3_125m_del 300 python3 "$R/tools/kbench.py" --docs 125000000 --reps 5 --only config3_url --deletes 0.01 &&
-              run bench_config3 300 python3 "$R/bench.py" --workload config3 --shards 8 --docs 125000000 --cpu-docs 0 ;;
+              run bench_config3 300 python3 "$R/bench.py" --full --workload config3 --shards 8 --docs 125000000 --cpu-docs 0 ;;
         hot16ab) # config 3 postings hot pass: 32-bit recoded column vs the 16-bit hot-slot column, clean and 1 % deleted
               for h in 0 1; do for d in 0 0.01; do
                   ESGPU_HOT16=$h run "kbench_c3_hot16_${h}_del$d" 300 python3 "$R/tools/kbench.py" --docs 125000000 --reps 7 \
@@ -120,12 +120,12 @@ for s in $STEPS; do
         smoke) run smoke 300 python3 -c "import sys; sys.path.insert(0, '$R'); import __graft_entry__ as g; g.smoke()" ;;
         inflightab) # requests in flight: 2 / 3 / 4 (north star 1 x 1B and 8 x 125M)
               for d in 2 3 4; do
-                  run "bench_if$d" 300 python3 "$R/bench.py" --inflight $d --cpu-docs 0 || exit 1
-                  run "bench_ns8_if$d" 300 python3 "$R/bench.py" --inflight $d --shards 8 --docs 125000000 --cpu-docs 0 || exit 1
+                  run "bench_if$d" 300 python3 "$R/bench.py" --full --inflight $d --cpu-docs 0 || exit 1
+                  run "bench_ns8_if$d" 300 python3 "$R/bench.py" --full --inflight $d --shards 8 --docs 125000000 --cpu-docs 0 || exit 1
               done ;;
         proftl) # kernel timeline of the default bench (2 requests in flight): GPU idle gaps between collect launches
               cd /tmp && run rocprof_timeline 600 rocprofv3 --kernel-trace --output-format csv -d "$OUT/proftl" -o bench -- \
-                  python3 "$R/bench.py" --steps 10 --warmup 3 --cpu-docs 0 ;;
+                  python3 "$R/bench.py" --full --steps 10 --warmup 3 --cpu-docs 0 ;;
         profk) cd /tmp && run rocprof_kbench 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/profk" -o kbench -- \
                    python3 "$R/tools/kbench.py" --docs 1000000000 --reps 3 ;;
         profk125) cd /tmp && run rocprof_kbench125 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/profk125" -o kb125 -- \
@@ -148,7 +148,7 @@ for s in $STEPS; do
                       --only hosts_urls || exit 1
               done; done ;;
         c3stats) # config 3: the per-segment statistics build (bench precomputed) and the filtered / deleted forms
-              run bench_config3 300 python3 "$R/bench.py" --workload config3 --shards 8 --docs 125000000 --cpu-docs 0 --steps 5 &&
+              run bench_config3 300 python3 "$R/bench.py" --full --workload config3 --shards 8 --docs 125000000 --cpu-docs 0 --steps 5 &&
               run kbench_c3_125m_del 300 python3 "$R/tools/kbench.py" --docs 125000000 --reps 5 --only config3_url --deletes 0.01 ;;
         profreplay) # kernel breakdown of the breadth-first replay (terms(host){terms(url)} at 1B docs)
               cd /tmp && run rocprof_replay 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/profreplay" -o kb -- \
@@ -156,9 +156,9 @@ for s in $STEPS; do
         testfile) run "pytest_${TESTFILE:-x}" 600 python3 -u -m pytest "$R/tests/${TESTFILE:-test_gpu_parity}.py" -m gpu -x -v \
                       -p no:cacheprovider --timeout 300 --timeout-method thread ;;
         pmc) cd /tmp && run pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_fetch" -o bench -- \
-                 python3 "$R/bench.py" --steps 3 --warmup 1 --cpu-docs 0 --inflight 1 &&
+                 python3 "$R/bench.py" --full --steps 3 --warmup 1 --cpu-docs 0 --inflight 1 &&
              run pmc_write 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_write" -o bench -- \
-                 python3 "$R/bench.py" --steps 3 --warmup 1 --cpu-docs 0 --inflight 1 ;;
+                 python3 "$R/bench.py" --full --steps 3 --warmup 1 --cpu-docs 0 --inflight 1 ;;
         pmcall) # FETCH_SIZE / WRITE_SIZE passes (one counter per pass) of every bench shape's collect, 4 collects each
                 # (kbench --reps 3), for tools/pmc_traffic.py -> profiles/hbm_traffic.json (bench roofline.traffic)
               for spec in north_star:1000000000 north_star:125000000 config2_dh_ext:100000000 config3_url:125000000 \
