@@ -97,6 +97,7 @@ AggBlock._fields_ = [
     ("lc_hashes", ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32))), ("lc_sizes", ctypes.POINTER(_I64)),
     ("order_path", ctypes.c_char_p),
     ("time_zone", ctypes.c_char_p), ("value_format", _I32), ("reserved_fmt", _I32), ("format", ctypes.c_char_p),
+    ("terms_kind", _I32), ("reserved_kind", _I32), ("term_longs", ctypes.POINTER(_I64)),  # 1 = LongTerms
 ]
 
 

@@ -71,6 +71,8 @@ struct esgpu_ctx {
     std::mutex mu;
     // layout options (esgpu_ctx_set_option): compact columns, packed integer metric cells
     std::atomic<int> opt_compact{1}, opt_pi{1}, opt_hll_fs{1}, opt_b16{1};
+    // distinct values of a long column in one segment above which terms over it are refused (numeric ordinals)
+    std::atomic<int64_t> opt_num_max{1ll << 22};
     // synthetic tables (device copies)
     double* d_host_cdf = nullptr;
     double* d_rt_cdf = nullptr;

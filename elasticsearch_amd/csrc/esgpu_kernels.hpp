@@ -414,6 +414,31 @@ void launch_minmax_i64(const int64_t* v, uint64_t n, int64_t* out, bool f64, hip
 void launch_widen_u32(const unsigned int* src, size_t n, unsigned long long* dst, hipStream_t st);
 void launch_narrow_u64(const unsigned long long* src, size_t n, unsigned int* dst, hipStream_t st);
 void launch_pack_ord16(const uint32_t* src, uint32_t n, uint16_t* out, hipStream_t st);
+// ---- numeric ordinals (esgpu_numord.hip): a long column's sorted distinct values and each doc's rank among them ----
+// `v` with `width` 8 is the upload-width column, 4 / 2 its d32 / d16 deltas over vmin; span = vmax - vmin; the bitmap
+// holds span / 64 + 1 zeroed 64-bit words.  Spans below kNumOrdLdsBits are marked in a per-workgroup LDS bitmap.
+constexpr uint64_t kNumOrdDenseSpan = 1ull << 26;  // dense path while vmax - vmin is below this
+constexpr uint64_t kNumOrdLdsBits = 1ull << 18;    // 32 KiB of LDS per workgroup
+void launch_numord_mark(const void* v, int width, const uint64_t* present, uint32_t n_docs, uint32_t n_pad, int64_t vmin,
+                        uint64_t span, uint32_t* bits, hipStream_t st);
+// chunk_sum: words / 1024 + 2 entries; on return the chunks' exclusive rank bases, then the distinct count
+void launch_numord_rank_sums(const uint64_t* bits, uint32_t words, uint32_t* chunk_sum, hipStream_t st);
+void launch_numord_rank_write(const uint64_t* bits, uint32_t words, const uint32_t* chunk_base, int64_t vmin, uint32_t n_dict,
+                              uint32_t* base, int64_t* dict, hipStream_t st);
+void launch_numord_encode_dense(const void* v, int width, const uint64_t* present, uint32_t n_docs, uint32_t n_pad, int64_t vmin,
+                                uint64_t span, const uint64_t* bits, const uint32_t* base, uint32_t* ord, hipStream_t st);
+// wide spans: an open-addressing set in `table` (`slots` a power of two, every byte 0xFF = empty; the long -1 is kept in
+// flags[kNumOrdFlagSentinel] instead); a full table or `probe_limit` probes set flags[kNumOrdFlagOverflow]
+enum { kNumOrdFlagSentinel = 0, kNumOrdFlagOverflow = 1 };
+void launch_numord_hash_insert(const int64_t* v, const uint64_t* present, uint32_t n_docs, unsigned long long* table, uint32_t slots,
+                               uint32_t probe_limit, uint32_t* flags, hipStream_t st);
+void launch_numord_hash_compact(const unsigned long long* table, uint32_t slots, uint32_t cap, int64_t* out, uint32_t* count,
+                                hipStream_t st);
+void launch_numord_hash_rank(const unsigned long long* table, uint32_t slots, const int64_t* dict, uint32_t n_dict, uint32_t* slot_rank,
+                             hipStream_t st);
+void launch_numord_encode_hash(const int64_t* v, const uint64_t* present, uint32_t n_docs, uint32_t n_pad,
+                               const unsigned long long* table, uint32_t slots, uint32_t probe_limit, const uint32_t* slot_rank,
+                               uint32_t sentinel_rank, uint32_t* ord, hipStream_t st);
 void launch_delta16(const int64_t* v, uint32_t n, int64_t base, uint16_t* out, hipStream_t st);
 void launch_delta32(const int64_t* v, uint32_t n, int64_t base, uint32_t* out, hipStream_t st);
 // breadth-first replay, compacted: one pass over a retained segment appends, for every doc whose outer bucket survived

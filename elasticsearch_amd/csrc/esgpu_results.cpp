@@ -263,6 +263,7 @@ Block Block::like() const {
     b.has_bmin = has_bmin; b.has_bmax = has_bmax; b.bmin = bmin; b.bmax = bmax;
     b.sigma = sigma; b.precision = precision; b.order_path = order_path;
     b.time_zone = time_zone; b.value_format = value_format; b.format = format;
+    b.terms_kind = terms_kind;
     b.n = 0;
     if (is_bucket()) {
         b.boff.assign(1, 0);
@@ -285,6 +286,7 @@ void Block::append_instance(const Block& src, uint64_t i) {
             key.push_back(src.key[k]);
             term_pool.append(src.term_pool, src.term_off[k], src.term_off[k + 1] - src.term_off[k]);
             term_off.push_back(term_pool.size());
+            if (terms_kind == 1) term_long.push_back(src.long_key(k));
             bcount.push_back(src.bcount[k]);
             berr.push_back(src.berr[k]);
         }
@@ -363,12 +365,21 @@ inline std::string_view term_of(const Block& b, uint64_t k) {
     return std::string_view(b.term_pool.data() + b.term_off[k], b.term_off[k + 1] - b.term_off[k]);
 }
 
-int cmp_terms(int order, int64_t ca, int64_t cb, std::string_view ta, std::string_view tb) {
+// compareTerm of two buckets: BytesRef.compareTo (unsigned bytes), or Long.compare for LongTerms (LongTerms.java:86-88)
+inline int cmp_term(bool longs, const Block& a, uint64_t ka, const Block& b, uint64_t kb) {
+    if (longs) {
+        const int64_t x = a.long_key(ka), y = b.long_key(kb);
+        return x < y ? -1 : x > y ? 1 : 0;
+    }
+    return term_of(a, ka).compare(term_of(b, kb));
+}
+
+int cmp_terms(int order, int64_t ca, int64_t cb, int term_cmp) {
     switch (order) {
-        case ESGPU_ORDER_COUNT_DESC: if (ca != cb) return ca > cb ? -1 : 1; return ta.compare(tb);
-        case ESGPU_ORDER_COUNT_ASC: if (ca != cb) return ca < cb ? -1 : 1; return ta.compare(tb);
-        case ESGPU_ORDER_TERM_DESC: return -ta.compare(tb);
-        default: return ta.compare(tb);
+        case ESGPU_ORDER_COUNT_DESC: if (ca != cb) return ca > cb ? -1 : 1; return term_cmp;
+        case ESGPU_ORDER_COUNT_ASC: if (ca != cb) return ca < cb ? -1 : 1; return term_cmp;
+        case ESGPU_ORDER_TERM_DESC: return -term_cmp;
+        default: return term_cmp;
     }
 }
 
@@ -404,6 +415,7 @@ struct Scratch {
     std::vector<OutBucket> buckets, filled;
     std::vector<uint32_t> ids, start;
     std::unordered_map<std::string_view, uint32_t> index;
+    std::unordered_map<int64_t, uint32_t> lindex;  // LongTerms: buckets by key
     std::vector<Ref> child;
     DenseKeys dense;
 };
@@ -530,6 +542,7 @@ void emit_buckets(Block& out, const std::vector<OutBucket>& buckets, const Scrat
             out.term_pool.append(t.data(), t.size());
         }
         out.term_off[t0 + q] = out.term_pool.size();
+        if (out.terms_kind == 1 && ob.tb) out.term_long.push_back(ob.tb->long_key(ob.tk));
         out.bcount[k0 + q] = ob.count;
         out.berr[k0 + q] = ob.err;
     }
@@ -579,6 +592,8 @@ void reduce_terms(const Ref* refs, size_t nrefs, Block& out, Scratch& sc, std::v
     sc.contrib.clear();
     sc.ids.clear();
     sc.index.clear();
+    sc.lindex.clear();
+    const bool longs = out.terms_kind == 1;
     std::vector<Ref>& entries = sc.child;  // (block, bucket) in shard order
     entries.clear();
     for (size_t x = 0; x < nrefs; ++x) {
@@ -597,9 +612,17 @@ void reduce_terms(const Ref* refs, size_t nrefs, Block& out, Scratch& sc, std::v
                 id = (uint32_t)sc.buckets.size();
                 sc.buckets.push_back(OutBucket{t.key[k], &t, k, 0, 0, 0, 0, false});
             } else {
-                auto ins = sc.index.try_emplace(term_of(t, k), (uint32_t)sc.buckets.size());
-                if (ins.second) sc.buckets.push_back(OutBucket{t.key[k], &t, k, 0, 0, 0, 0, false});
-                id = ins.first->second;
+                bool fresh;
+                if (longs) {  // LongTerms.doReduce groups the buckets by their long key
+                    auto ins = sc.lindex.try_emplace(t.long_key(k), (uint32_t)sc.buckets.size());
+                    fresh = ins.second;
+                    id = ins.first->second;
+                } else {
+                    auto ins = sc.index.try_emplace(term_of(t, k), (uint32_t)sc.buckets.size());
+                    fresh = ins.second;
+                    id = ins.first->second;
+                }
+                if (fresh) sc.buckets.push_back(OutBucket{t.key[k], &t, k, 0, 0, 0, 0, false});
             }
             OutBucket& ob = sc.buckets[id];
             ob.count += t.bcount[k];
@@ -672,9 +695,9 @@ void reduce_terms(const Ref* refs, size_t nrefs, Block& out, Scratch& sc, std::v
         if (agg_order) {
             const int c = compare_discard_nan(vals[a.val], vals[b.val], out.order == ESGPU_ORDER_AGG_ASC);
             if (c != 0) return c < 0;
-            return term_of(*a.tb, a.tk).compare(term_of(*b.tb, b.tk)) < 0;
+            return cmp_term(longs, *a.tb, a.tk, *b.tb, b.tk) < 0;
         }
-        return cmp_terms(out.order, a.count, b.count, term_of(*a.tb, a.tk), term_of(*b.tb, b.tk)) < 0;
+        return cmp_terms(out.order, a.count, b.count, cmp_term(longs, *a.tb, a.tk, *b.tb, b.tk)) < 0;
     };
     if (sc.buckets.size() > size) {
         std::partial_sort(sc.buckets.begin(), sc.buckets.begin() + size, sc.buckets.end(), less);
@@ -924,6 +947,7 @@ void copy_verbatim(const Ref& r, Block& out, std::vector<Level>& child) {
         const std::string_view t = term_of(src, k);
         out.term_pool.append(t.data(), t.size());
         out.term_off.push_back(out.term_pool.size());
+        if (out.terms_kind == 1) out.term_long.push_back(src.long_key(k));
         out.bcount.push_back(src.bcount[k]);
         out.berr.push_back(src.berr[k]);
         for (size_t j = 0; j < out.subs.size(); ++j) {
@@ -1015,12 +1039,48 @@ void reduce_level(const Level& lv, Block& out) {
 
 }  // namespace
 
+void merge_long_dicts(const std::vector<const std::vector<int64_t>*>& segs, std::vector<int64_t>& global,
+                      std::vector<std::vector<uint32_t>>& maps) {
+    global.clear();
+    maps.assign(segs.size(), {});
+    for (const std::vector<int64_t>* d : segs) {
+        if (!d) continue;
+        const size_t at = global.size();
+        global.insert(global.end(), d->begin(), d->end());
+        std::inplace_merge(global.begin(), global.begin() + at, global.end());
+    }
+    global.erase(std::unique(global.begin(), global.end()), global.end());
+    for (size_t k = 0; k < segs.size(); ++k) {
+        if (!segs[k]) continue;
+        const std::vector<int64_t>& own = *segs[k];
+        maps[k].resize(own.size());
+        size_t at = 0;
+        for (size_t o = 0; o < own.size(); ++o) {  // both ascending: one forward walk
+            if (o && own[o] <= own[o - 1]) throw std::invalid_argument("numeric dictionary not strictly sorted");
+            while (global[at] != own[o]) ++at;
+            maps[k][o] = (uint32_t)at;
+        }
+    }
+}
+
 // shard results of one request share the aggregation tree (types, sub-aggregation lists, sketch precision)
 bool same_shape(const Block& a, const Block& b) {
     if (a.type != b.type || a.subs.size() != b.subs.size() || a.empty_subs.size() != b.empty_subs.size()) return false;
     if (a.type == ESGPU_AGG_CARDINALITY && a.precision != b.precision) return false;
     for (size_t j = 0; j < a.subs.size(); ++j) if (!same_shape(a.subs[j], b.subs[j])) return false;
     return true;
+}
+
+// A shard whose segments lack a long field builds its (empty) terms as string terms: the reduced tree is LongTerms
+// wherever some shard's is, with that shard's formatter
+static void adopt_kinds(Block& out, const Block& in) {
+    if (in.type == ESGPU_AGG_TERMS && in.terms_kind == 1 && out.terms_kind != 1) {
+        out.terms_kind = 1;
+        out.value_format = in.value_format;
+        out.format = in.format;
+        out.time_zone = in.time_zone;
+    }
+    for (size_t j = 0; j < out.subs.size() && j < in.subs.size(); ++j) adopt_kinds(out.subs[j], in.subs[j]);
 }
 
 std::vector<Block> reduce_lists(const std::vector<const std::vector<Block>*>& lists) {
@@ -1036,6 +1096,7 @@ std::vector<Block> reduce_lists(const std::vector<const std::vector<Block>*>& li
         }
         lv.groups.push_back(Group{0, (uint32_t)lv.pool.size(), false});
         Block b = (*lists[0])[a].like();
+        for (auto* l : lists) adopt_kinds(b, (*l)[a]);
         reduce_level(lv, b);
         out.push_back(std::move(b));
     }
@@ -1088,6 +1149,15 @@ uint64_t fnv1a(const uint8_t* p, size_t n) {
     return h;
 }
 
+std::string es_date(int64_t ms, const std::vector<int64_t>& starts, const std::vector<int64_t>& offs);
+// ValueFormatter.format of a LongTerms key whose formatter is not RAW: a date field's keys print like date_histogram
+// keys (the mapping's default printer, UTC: a terms aggregation has no time zone); a number pattern is not rendered
+// (no DecimalFormat here) and prints the decimal value
+std::string long_key_string(const Block& a, uint64_t k) {
+    if (a.value_format == ESGPU_FORMAT_DATE_TIME) return es_date(a.long_key(k), {}, {});
+    return std::to_string((long long)a.long_key(k));
+}
+
 void write_instance(J& j, const Block& a, uint64_t i);
 
 void write_subs(J& j, const Block& a, uint64_t k) {
@@ -1107,7 +1177,14 @@ void write_instance(J& j, const Block& a, uint64_t i) {
             j.key("buckets"); j.raw("[");
             for (uint64_t k = a.boff[i]; k < a.boff[i + 1]; ++k) {
                 if (k != a.boff[i]) j.raw(",");
-                j.raw("{"); j.key("key"); j.str(a.term_pool.data() + a.term_off[k], a.term_off[k + 1] - a.term_off[k]); j.raw(",");
+                j.raw("{"); j.key("key");
+                if (a.terms_kind == 1) {
+                    j.i64(a.long_key(k));
+                    if (a.value_format != ESGPU_FORMAT_RAW) { j.raw(","); j.key("key_as_string"); j.str(long_key_string(a, k)); }
+                } else {
+                    j.str(a.term_pool.data() + a.term_off[k], a.term_off[k + 1] - a.term_off[k]);
+                }
+                j.raw(",");
                 j.key("doc_count"); j.i64(a.bcount[k]);
                 if (a.show_err) { j.raw(","); j.key("doc_count_error_upper_bound"); j.i64(a.berr[k]); }
                 write_subs(j, a, k);
@@ -1293,7 +1370,14 @@ void x_instance(X& x, const Block& a, uint64_t i) {
             x.key("buckets"); x.raw("[");
             for (uint64_t k = a.boff[i]; k < a.boff[i + 1]; ++k) {
                 if (k != a.boff[i]) x.raw(",");
-                x.raw("{"); x.key("key"); x.str(a.term_pool.data() + a.term_off[k], a.term_off[k + 1] - a.term_off[k]); x.raw(",");
+                x.raw("{"); x.key("key");
+                if (a.terms_kind == 1) {  // LongTerms.Bucket.toXContent (LongTerms.java:139-152)
+                    x.i64(a.long_key(k));
+                    if (a.value_format != ESGPU_FORMAT_RAW) { x.raw(","); x.key("key_as_string"); x.str(long_key_string(a, k)); }
+                } else {
+                    x.str(a.term_pool.data() + a.term_off[k], a.term_off[k + 1] - a.term_off[k]);
+                }
+                x.raw(",");
                 x.key("doc_count"); x.i64(a.bcount[k]);
                 if (a.show_err) { x.raw(","); x.key("doc_count_error_upper_bound"); x.i64(a.berr[k]); }
                 x_subs(x, a, k);
@@ -1514,6 +1598,7 @@ void es_instance(JavaOut& w, const Block& a, uint64_t i) {
         case ESGPU_AGG_TERMS: {  // StringTerms.doWriteTo (:205-217), Bucket.writeTo (:128-136)
             w.i64(a.doc_count_error[i]);
             write_terms_order(w, a);
+            if (a.terms_kind == 1) write_formatter(w, a);  // LongTerms.doWriteTo (LongTerms.java:214-227)
             w.size(a.required_size);
             w.size(a.shard_size);
             w.boolean(a.show_err != 0);
@@ -1522,7 +1607,8 @@ void es_instance(JavaOut& w, const Block& a, uint64_t i) {
             const uint64_t b0 = a.boff[i], b1 = a.boff[i + 1];
             w.vint((int32_t)(b1 - b0));
             for (uint64_t b = b0; b < b1; ++b) {
-                w.bytes_ref(a.term_pool.data() + a.term_off[b], a.term_off[b + 1] - a.term_off[b]);
+                if (a.terms_kind == 1) w.i64(a.long_key(b));  // LongTerms.Bucket.writeTo (:129-136)
+                else w.bytes_ref(a.term_pool.data() + a.term_off[b], a.term_off[b + 1] - a.term_off[b]);
                 w.vlong(a.bcount[b]);
                 if (a.show_err) w.i64(a.berr[b]);
                 es_list(w, a.subs, b);
@@ -1603,7 +1689,7 @@ void es_instance(JavaOut& w, const Block& a, uint64_t i) {
 void es_list(JavaOut& w, const std::vector<Block>& l, uint64_t i) {
     w.vint((int32_t)l.size());
     for (const Block& a : l) {
-        const char* t = stream_type(a.type);
+        const char* t = a.type == ESGPU_AGG_TERMS && a.terms_kind == 1 ? "lterms" : stream_type(a.type);  // LongTerms.java:44
         w.bytes_ref(t, std::strlen(t));
         es_instance(w, a, i);
     }
@@ -1622,6 +1708,7 @@ void to_es_stream(const std::vector<Block>& aggs, std::string& out) {
 namespace {
 struct W {
     std::string& o;
+    uint32_t version = 5;
     template <class T> void pod(const T& v) { o.append((const char*)&v, sizeof v); }
     void str(const std::string& s) { pod<uint64_t>(s.size()); o.append(s); }
     template <class T> void vec(const std::vector<T>& v) {
@@ -1632,6 +1719,7 @@ struct W {
 struct R {
     const uint8_t* p;
     size_t n, i = 0;
+    uint32_t version = 5;
     template <class T> T pod() {
         if (i + sizeof(T) > n) throw std::runtime_error("truncated stream");
         T v;
@@ -1665,6 +1753,7 @@ void w_block(W& w, const Block& a) {
     w.str(a.time_zone); w.pod(a.value_format); w.str(a.format); w.pod(a.n);
     w.vec(a.doc_count_error); w.vec(a.other_doc_count); w.vec(a.boff); w.vec(a.key); w.vec(a.term_off);
     w.str(a.term_pool); w.vec(a.bcount); w.vec(a.berr);
+    if (w.version >= 6) { w.pod(a.terms_kind); w.vec(a.term_long); }
     w_blocks(w, a.subs);
     w_blocks(w, a.empty_subs);
     w.vec(a.count); w.vec(a.sum); w.vec(a.min); w.vec(a.max); w.vec(a.sumsq);
@@ -1693,6 +1782,7 @@ void r_block(R& r, Block& a, int depth) {
     a.time_zone = r.str(); a.value_format = r.pod<int32_t>(); a.format = r.str(); a.n = r.pod<uint64_t>();
     r.vec(a.doc_count_error); r.vec(a.other_doc_count); r.vec(a.boff); r.vec(a.key); r.vec(a.term_off);
     a.term_pool = r.str(); r.vec(a.bcount); r.vec(a.berr);
+    if (r.version >= 6) { a.terms_kind = r.pod<int32_t>(); r.vec(a.term_long); }
     r_blocks(r, a.subs, depth + 1);
     r_blocks(r, a.empty_subs, depth + 1);
     r.vec(a.count); r.vec(a.sum); r.vec(a.min); r.vec(a.max); r.vec(a.sumsq);
@@ -1703,12 +1793,15 @@ void r_block(R& r, Block& a, int depth) {
     for (auto& x : a.lc) r.vec(x);
     // structural validation: a corrupt record must not produce out-of-bounds views
     const bool bucket = a.is_bucket();
+    if (!bucket && (a.terms_kind != 0 || !a.term_long.empty())) throw std::runtime_error("long terms fields on a block without buckets");
     if (bucket) {
         const uint64_t nb = a.boff.empty() ? 0 : a.boff.back();
         if (a.boff.size() != a.n + 1 || a.key.size() != nb || a.bcount.size() != nb || a.berr.size() != nb ||
             a.term_off.size() != nb + 1 || a.doc_count_error.size() != a.n || a.other_doc_count.size() != a.n ||
             (nb && a.term_off.back() != a.term_pool.size()))
             throw std::runtime_error("inconsistent bucket block");
+        if (a.terms_kind != 0 && !(a.terms_kind == 1 && a.type == ESGPU_AGG_TERMS)) throw std::runtime_error("bad terms kind");
+        if (a.term_long.size() != (a.terms_kind == 1 ? nb : 0)) throw std::runtime_error("inconsistent long terms block");
         for (size_t k = 0; k + 1 < a.boff.size(); ++k) if (a.boff[k] > a.boff[k + 1]) throw std::runtime_error("bad offsets");
         for (size_t k = 0; k + 1 < a.term_off.size(); ++k) if (a.term_off[k] > a.term_off[k + 1]) throw std::runtime_error("bad offsets");
         for (const Block& s : a.subs) if (s.n != nb) throw std::runtime_error("sub-aggregation instance count mismatch");
@@ -1746,21 +1839,29 @@ void r_blocks(R& r, std::vector<Block>& l, int depth) {
     for (Block& a : l) r_block(r, a, depth);
 }
 const uint32_t kStreamMagic = 0x45534750;  // "ESGP"
-const uint32_t kStreamVersion = 5;
+// version 6 = version 5 plus, per block, the terms kind and the long keys; written only when a result holds LongTerms
+const uint32_t kStreamVersion = 5, kStreamVersionLongTerms = 6;
+bool has_long_terms(const std::vector<Block>& l) {
+    for (const Block& a : l)
+        if (a.terms_kind == 1 || has_long_terms(a.subs) || has_long_terms(a.empty_subs)) return true;
+    return false;
+}
 }  // namespace
 
 void serialize(const std::vector<Block>& aggs, std::string& out) {
     out.clear();
     W w{out};
+    w.version = has_long_terms(aggs) ? kStreamVersionLongTerms : kStreamVersion;
     w.pod(kStreamMagic);
-    w.pod(kStreamVersion);
+    w.pod(w.version);
     w_blocks(w, aggs);
 }
 
 bool deserialize(const uint8_t* p, size_t n, std::vector<Block>& out) {
     R r{p, n};
     if (n < 8 || r.pod<uint32_t>() != kStreamMagic) return false;
-    if (r.pod<uint32_t>() != kStreamVersion) return false;
+    r.version = r.pod<uint32_t>();
+    if (r.version != kStreamVersion && r.version != kStreamVersionLongTerms) return false;
     r_blocks(r, out, 0);
     for (const Block& b : out) if (b.n != 1) throw std::runtime_error("top-level aggregations carry one instance");
     return true;
@@ -1800,6 +1901,8 @@ void export_block(ResultHolder& h, const Block& a, esgpu_agg_block& o) {
     o.time_zone = a.time_zone.c_str();
     o.value_format = a.value_format;
     o.format = a.format.c_str();
+    o.terms_kind = a.terms_kind;
+    o.term_longs = ptr(a.term_long);
     o.nsubs = (int32_t)a.subs.size();
     o.n_instances = a.n;
     o.doc_count_error = ptr(a.doc_count_error);
@@ -1956,6 +2059,7 @@ Block terms_skeleton(const Block& t) {
     s.key = t.key;
     s.term_off = t.term_off;
     s.term_pool = t.term_pool;
+    s.term_long = t.term_long;
     s.bcount = t.bcount;
     s.berr = t.berr;
     for (Block& sub : s.subs)

@@ -11,7 +11,9 @@
 #include <stdint.h>
 
 #include <memory>
+#include <stdexcept>
 #include <string>
+#include <string_view>
 #include <vector>
 
 #include "../../include/esgpu.h"
@@ -52,6 +54,8 @@ struct Block {
     std::vector<int64_t> key;              // [nb] histogram key / terms ordinal in the producing shard
     std::vector<uint64_t> term_off;        // [nb + 1] (terms)
     std::string term_pool;
+    int32_t terms_kind = 0;                // terms: 0 = StringTerms, 1 = LongTerms (a long / date field)
+    std::vector<int64_t> term_long;        // [nb] terms_kind 1: the key (term_pool holds its decimal text)
     std::vector<int64_t> bcount;           // [nb] doc_count
     std::vector<int64_t> berr;             // [nb] bucket doc_count_error
     std::vector<Block> subs;               // each with n == nb
@@ -70,6 +74,13 @@ struct Block {
     Rounding rounding() const;  // histogram specs: the request's Rounding (EmptyBucketInfo)
     bool is_bucket() const { return type == ESGPU_AGG_TERMS || type == ESGPU_AGG_HISTOGRAM || type == ESGPU_AGG_DATE_HISTOGRAM; }
     uint64_t nbuckets() const { return boff.empty() ? 0 : boff.back(); }
+    // terms_kind 1: bucket b's key.  A StringTerms block met where LongTerms are reduced (a field mapped as keyword on
+    // one shard and as long on another, or an old result) fails the reduce like every other mismatch of the trees.
+    int64_t long_key(uint64_t b) const {
+        if (terms_kind != 1 || b >= term_long.size())
+            throw std::invalid_argument("aggregation trees differ across shards: string terms [" + name + "] where long terms are reduced");
+        return term_long[b];
+    }
     std::string term(uint64_t b) const { return term_pool.substr(term_off[b], term_off[b + 1] - term_off[b]); }
 
     // an empty block with this block's parameters and sub-structure (no instances)
@@ -80,6 +91,11 @@ struct Block {
     void append_empty();
 };
 
+
+// The reader-wide numeric dictionary of an ordinal map over a long field: the union of the segments' sorted distinct
+// values (null: the segment lacks the field) in numeric order, and per segment its local -> global ordinal table.
+void merge_long_dicts(const std::vector<const std::vector<int64_t>*>& segs, std::vector<int64_t>& global,
+                      std::vector<std::vector<uint32_t>>& maps);
 
 // ---- terms ordered by a metric sub-aggregation (InternalOrder.Aggregation) ----
 // AggregationPath.parse of a one-element path: "name", "name.key" or "name[key]" (key empty when absent)

@@ -30,6 +30,7 @@
 #include <condition_variable>
 #include <thread>
 #include <stdexcept>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -82,6 +83,11 @@ extern "C" int esgpu_ctx_set_option(esgpu_ctx* c, int32_t option, int64_t value)
             c->opt_hll_fs = (int)value;
             return;
         }
+        if (option == ESGPU_OPT_NUMERIC_TERMS_MAX_DISTINCT) {
+            require(value >= 1 && value <= (1ll << 30), ESGPU_ERR_INVALID, "numeric terms distinct-value cap must be 1..2^30");
+            c->opt_num_max = value;
+            return;
+        }
         require(value == 0 || value == 1, ESGPU_ERR_INVALID, "option value must be 0 or 1");
         if (option == ESGPU_OPT_COMPACT_COLUMNS) c->opt_compact = (int)value;
         else if (option == ESGPU_OPT_PACKED_METRIC) c->opt_pi = (int)value;
@@ -97,6 +103,7 @@ extern "C" int esgpu_ctx_get_option(const esgpu_ctx* c, int32_t option, int64_t*
         else if (option == ESGPU_OPT_PACKED_METRIC) *value = c->opt_pi;
         else if (option == ESGPU_OPT_HLL_FLOOR) *value = c->opt_hll_fs;
         else if (option == ESGPU_OPT_BLOCK_DELTAS) *value = c->opt_b16;
+        else if (option == ESGPU_OPT_NUMERIC_TERMS_MAX_DISTINCT) *value = c->opt_num_max;
         else throw EsError(ESGPU_ERR_INVALID, "unknown context option");
     });
 }
@@ -248,6 +255,8 @@ extern "C" int esgpu_synthetic_fill_host(uint64_t seed, uint32_t shard, uint32_t
 struct TermDict {
     uint32_t synth_bit = 0;          // synthetic formula (esgpu_synthetic_term)
     bool numbered = false;           // no term bytes given: term(ord) = decimal ordinal
+    bool numeric = false;            // a long field's distinct values, ascending (longs): term(ord) = decimal value
+    std::vector<int64_t> longs;      // n (numeric dictionaries)
     uint64_t n = 0;
     std::vector<uint8_t> bytes;
     std::vector<uint64_t> offsets;   // n + 1 (explicit dictionaries)
@@ -264,6 +273,10 @@ struct TermDict {
             scratch = std::to_string(o);
             return scratch;
         }
+        if (numeric) {
+            scratch = std::to_string((long long)longs[o]);
+            return scratch;
+        }
         return std::string_view((const char*)bytes.data() + offsets[o], (size_t)(offsets[o + 1] - offsets[o]));
     }
     std::string term(uint64_t o) const {
@@ -276,9 +289,10 @@ struct TermDict {
             const uint8_t* b = (const uint8_t*)p;
             for (size_t i = 0; i < len; ++i) { h ^= b[i]; h *= 0x100000001b3ULL; }
         };
-        const uint32_t kind = synth_bit ? synth_bit : numbered ? 0x80000000u : 0x40000000u;
+        const uint32_t kind = synth_bit ? synth_bit : numbered ? 0x80000000u : numeric ? 0x20000000u : 0x40000000u;
         mix(&kind, sizeof kind);
         mix(&n, sizeof n);
+        if (!longs.empty()) mix(longs.data(), longs.size() * 8);
         if (!offsets.empty()) mix(offsets.data(), offsets.size() * 8);
         if (!bytes.empty()) mix(bytes.data(), bytes.size());
         identity = h;
@@ -338,6 +352,14 @@ struct DevColumn {
     // the most frequent ordinal of ords() in a sample (a hint for the packed cells' register run; any value is correct)
     uint32_t hot_ord[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
     const void* hot_src = nullptr;
+    // numeric ordinals of a single-valued long column (ensure_num_ords, built on first use and cached with the column):
+    // an ORD_U32 column over the segment's numeric dictionary -- the rank of each doc's value among the distinct values
+    // of ALL the segment's docs -- which terms over the field count by like a keyword column (global ordinals included)
+    std::unique_ptr<DevColumn> num_view;
+    const DevColumn* num_src = nullptr;  // on the view: the long column it was built from
+    // the dictionary on the device (sorted longs): part of the product; after the build no kernel reads it yet (terms are
+    // resolved on the host through dict->longs)
+    DevBuf num_dict;
 
     const DevBuf& ords() const { return gdict ? gvalues : values; }       // what terms aggregations count by
     uint64_t ord_count() const { return gdict ? gdict->count() : value_count; }
@@ -363,6 +385,7 @@ struct esgpu_segment {
 };
 
 static const void* wide_i64(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
+static DevColumn* ensure_num_ords(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
 
 // the synthetic dictionaries (host-%04d / /p/%08x) are formulas: one shared instance per field
 static std::shared_ptr<const TermDict> synth_dict(uint32_t bit, uint64_t n) {
@@ -655,12 +678,17 @@ extern "C" int esgpu_ordinal_map_build(esgpu_ctx* ctx, esgpu_segment* const* seg
         require(ctx && segs && nsegs >= 1 && field && out, ESGPU_ERR_INVALID, "bad ordinal map arguments");
         HIPX(hipSetDevice(ctx->device));
         std::vector<DevColumn*> cols;
+        bool numeric = false;
         for (int i = 0; i < nsegs; ++i) {
             require(segs[i] != nullptr, ESGPU_ERR_INVALID, "null segment");
             auto it = segs[i]->cols.find(field);
             if (it == segs[i]->cols.end()) { cols.push_back(nullptr); continue; }  // unmapped in this segment
             DevColumn* c = it->second.get();
-            require(c->type == ESGPU_COL_ORD_U32, ESGPU_ERR_INVALID, "ordinal maps cover keyword columns");
+            if (c->type == ESGPU_COL_I64 && !c->multi) {  // a long field: the segment's numeric ordinals
+                c = ensure_num_ords(ctx, c, segs[i], ctx->stream);
+                numeric = true;
+            }
+            require(c->type == ESGPU_COL_ORD_U32, ESGPU_ERR_INVALID, "ordinal maps cover keyword and single-valued long columns");
             require(c->dict && !c->dict->numbered, ESGPU_ERR_INVALID, std::string("no term dictionary for ") + field);
             cols.push_back(c);
         }
@@ -668,6 +696,18 @@ extern "C" int esgpu_ordinal_map_build(esgpu_ctx* ctx, esgpu_segment* const* seg
         auto g = std::make_shared<TermDict>();
         g->offsets.push_back(0);
         std::vector<std::vector<uint32_t>> maps(cols.size());
+        if (numeric) {  // sorted longs: the union in numeric order, each segment's value at its rank in it
+            g->offsets.clear();
+            g->numeric = true;
+            std::vector<const std::vector<int64_t>*> dicts;
+            for (DevColumn* c : cols) {
+                require(!c || c->dict->numeric, ESGPU_ERR_INVALID, std::string("segments map [") + field + "] to different types");
+                dicts.push_back(c ? &c->dict->longs : nullptr);
+            }
+            merge_long_dicts(dicts, g->longs, maps);
+            g->n = g->longs.size();
+            require(g->count() < 0xFFFFFFFFull, ESGPU_ERR_UNSUPPORTED, "more than 2^32-1 global ordinals");
+        }
         std::vector<uint64_t> pos(cols.size(), 0);
         std::vector<std::string> cur(cols.size()), scratch(cols.size());
         using Item = std::pair<std::string_view, int>;
@@ -675,6 +715,8 @@ extern "C" int esgpu_ordinal_map_build(esgpu_ctx* ctx, esgpu_segment* const* seg
         std::priority_queue<Item, std::vector<Item>, decltype(cmp)> heap(cmp);
         for (size_t k = 0; k < cols.size(); ++k) {
             if (!cols[k]) continue;
+            if (numeric) continue;
+            require(!cols[k]->dict->numeric, ESGPU_ERR_INVALID, std::string("segments map [") + field + "] to different types");
             maps[k].resize(cols[k]->value_count);
             if (cols[k]->value_count) heap.push({dict_view(cols[k], 0, scratch[k]), (int)k});
         }
@@ -738,6 +780,7 @@ extern "C" int esgpu_ordinal_map_lookup(const esgpu_ordinal_map* m, const uint8_
     return guarded([&] {
         require(m && ord && (term || len == 0), ESGPU_ERR_INVALID, "null argument");
         const TermDict& d = *m->dict;
+        require(!d.numeric, ESGPU_ERR_INVALID, "an ordinal map over a long field has no terms to look up");
         const std::string_view key((const char*)term, len);
         uint64_t lo = 0, hi = d.count();
         while (lo < hi) {  // lower bound in unsigned byte order
@@ -1081,6 +1124,7 @@ struct esgpu_plan {
     std::vector<SpecNode> specs;
     std::vector<esgpu_filter> filters;
     std::vector<std::string> filter_fields;
+    std::set<std::string> long_fields;         // terms fields that resolved to a long column's numeric ordinals (LongTerms)
     std::vector<int> filter_owner;             // -1 = query clause (bool.filter); k = clause of filter aggregation spec k
     std::vector<std::string> filter_lo, filter_hi;  // owned copies of keyword range bounds (the caller's may not outlive create)
     std::vector<int> tops;                     // top-level spec indices in request order
@@ -1739,6 +1783,7 @@ static bool b16_on(const esgpu_ctx* c);
 static bool pi_cells(const esgpu_ctx* c);
 static uint32_t pi_copies(int met);
 static const uint16_t* ensure_ord16(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
+static const DevColumn* terms_col(esgpu_plan* p, const esgpu_segment* s, const std::string& field);
 static const uint32_t* ensure_d32(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
 static const uint16_t* ensure_d16(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
 static const DevColumn* ensure_b16(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
@@ -2736,11 +2781,9 @@ static const DevColumn* derive_hist_ords(esgpu_plan* p, Pipeline& pl, const esgp
 static uint64_t replay_stride(uint64_t vcB) { return (std::max<uint64_t>(vcB, 1) + 3) & ~3ull; }
 
 static const DevColumn* derive_comp_ords(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s) {
-    const DevColumn* a = s->col(pl.ord_field.c_str());
-    const DevColumn* b = s->col(pl.ord_field2.c_str());
+    const DevColumn* a = terms_col(p, s, pl.ord_field);
+    const DevColumn* b = terms_col(p, s, pl.ord_field2);
     if (!a || !b) return nullptr;
-    require(a->type == ESGPU_COL_ORD_U32 && b->type == ESGPU_COL_ORD_U32, ESGPU_ERR_UNSUPPORTED,
-            "terms on numeric fields run on the CPU path");
     require(!a->multi && !b->multi, ESGPU_ERR_UNSUPPORTED, "multi-valued terms fields three bucket levels deep run on the CPU path");
     if (pl.fresh || !pl.tdict) {
         pl.tdict = a->ord_dict();
@@ -2831,8 +2874,8 @@ static std::vector<uint32_t> hashset_values(std::vector<std::pair<uint64_t, uint
 
 static void collect_cards(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, const uint64_t* d_accept) {
     const bool ORD = pl.term_spec >= 0, HIST = pl.hist_spec >= 0;
-    const DevColumn* oc = ORD ? (pl.ord_hist || pl.comp ? pl.ord_col.get() : s->col(pl.ord_field.c_str())) : nullptr;
-    const DevColumn* hc = HIST ? s->col(pl.hist_field.c_str()) : nullptr;
+    const DevColumn* oc = ORD ? (pl.ord_hist || pl.comp ? pl.ord_col.get() : terms_col(p, s, pl.ord_field)) : nullptr;
+    const DevColumn* hc = !HIST ? nullptr : pl.inner_terms ? terms_col(p, s, pl.hist_field) : s->col(pl.hist_field.c_str());
     CollectParams G{};
     G.n_docs = s->max_doc;
     G.ord = oc ? oc->ords().as<uint32_t>() : nullptr;
@@ -2940,9 +2983,9 @@ static uint64_t defer_cells() {
 static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, const uint64_t* d_accept) {
     const bool ORD = pl.term_spec >= 0, HIST = pl.hist_spec >= 0;
     const DevColumn* oc = !ORD ? nullptr : pl.ord_hist ? derive_hist_ords(p, pl, s, false)
-                        : pl.comp ? derive_comp_ords(p, pl, s) : s->col(pl.ord_field.c_str());
+                        : pl.comp ? derive_comp_ords(p, pl, s) : terms_col(p, s, pl.ord_field);
     if (pl.comp && !oc) return 0;
-    const DevColumn* hc = HIST ? s->col(pl.hist_field.c_str()) : nullptr;
+    const DevColumn* hc = !HIST ? nullptr : pl.inner_terms ? terms_col(p, s, pl.hist_field) : s->col(pl.hist_field.c_str());
     const DevColumn* mc = pl.met > 0 ? s->col(pl.metric_field.c_str()) : nullptr;
     const bool terms_outer = pl.outer == pl.term_spec;
     if (pl.inner_terms && pl.fresh) pl.deferred = false;
@@ -2967,10 +3010,7 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
     // aggregation of those docs is empty.  A deferred pipeline collects the same way: only the outer doc counts.
     const bool inner_missing = ORD && HIST && ((pl.deferred && oc) || (terms_outer ? (oc && !hc) : (hc && !oc)));
     if (((ORD && !oc) || (HIST && !hc)) && !inner_missing) return 0;
-    if (oc) require(oc->type == ESGPU_COL_ORD_U32, ESGPU_ERR_UNSUPPORTED, "terms on numeric fields run on the CPU path");
-    if (hc && pl.inner_terms) {  // multi-valued outer / inner fields take the CSR kernel (inner ordinals as keys)
-        require(hc->type == ESGPU_COL_ORD_U32, ESGPU_ERR_UNSUPPORTED, "terms on numeric fields run on the CPU path");
-    } else if (hc) {
+    if (hc && !pl.inner_terms) {  // (terms fields: keyword ordinals or a long column's numeric ordinals, terms_col)
         require(hc->type == ESGPU_COL_I64 || hc->type == ESGPU_COL_F64, ESGPU_ERR_UNSUPPORTED,
                 "histogram over a keyword field runs on the CPU path");
     }
@@ -3210,7 +3250,7 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
     const DevColumn* t16 = nullptr;  // the key column's block deltas (ensure_b16)
     bool tcomp = false;              // the key column is read as compact deltas (32-bit, or block deltas)
     if (compact_cols(p->ctx)) {
-        const bool plain_ord = oc && !pl.comp && !pl.ord_hist && oc == s->col(pl.ord_field.c_str());
+        const bool plain_ord = oc && !pl.comp && !pl.ord_hist && (oc->num_src ? oc->num_src : oc) == s->col(pl.ord_field.c_str());
         if (L_ORD && P.ord && plain_ord && !oc->multi && oc->ord_count() < 0xFFFFu) {
             P.ord16 = ensure_ord16(p->ctx, oc, s, p->stream);
             if (P.ord16) bytes_per_doc -= 2;
@@ -3800,6 +3840,123 @@ static const uint16_t* ensure_d16(esgpu_ctx* c, const DevColumn* col, const esgp
     return m->d16.as<uint16_t>();
 }
 
+// ---- numeric ordinals (terms over long / date fields, LongTermsAggregator.java:78-107) ----
+// The segment's numeric dictionary -- the sorted distinct values of ALL its docs, whatever a request filters, as the
+// min_doc_count == 0 fill-in of the reference walks every doc of the reader (:113-125) -- and each doc's rank in it, as
+// an ordinal column every terms form of keyword fields counts by.  Dense spans go through a presence bitmap, wide ones
+// through a hash set whose distinct values the host sorts (std::sort: once per segment).  (the caller holds c->mu)
+static std::unique_ptr<DevColumn> build_num_ords(esgpu_ctx* c, DevColumn* m, const esgpu_segment* s, hipStream_t st, DevBuf& ddict) {
+    std::unique_ptr<DevColumn> view(new DevColumn());
+    view->name = m->name;
+    view->type = ESGPU_COL_ORD_U32;
+    view->num_src = m;
+    view->values.alloc(c, (size_t)s->n_pad * 4);
+    auto td = std::make_shared<TermDict>();
+    td->numeric = true;
+    const uint64_t* present = m->present.as<uint64_t>();
+    const uint64_t cap = (uint64_t)c->opt_num_max.load();
+    const std::string over = "terms over a numeric field with more than " + std::to_string(cap) +
+                             " distinct values in a segment run on the CPU path";
+    if (s->max_doc == 0 || m->vmin > m->vmax) {  // no doc has a value
+        if (s->n_pad) HIPX(hipMemsetAsync(view->values.p, 0xFF, view->values.bytes, st));
+    } else if ((uint64_t)m->vmax - (uint64_t)m->vmin < kNumOrdDenseSpan) {
+        const uint64_t span = (uint64_t)m->vmax - (uint64_t)m->vmin;
+        const uint32_t words = (uint32_t)(span / 64 + 1), chunks = (words + 1023) / 1024;
+        const void* src = m->d16.p ? m->d16.p : m->d32.p ? m->d32.p : wide_i64_locked(c, m, s, st);
+        const int width = m->d16.p ? 2 : m->d32.p ? 4 : 8;
+        DevBuf bits, base, sums;
+        bits.alloc(c, (size_t)words * 8);
+        base.alloc(c, (size_t)words * 4);
+        sums.alloc(c, ((size_t)chunks + 2) * 4);
+        HIPX(hipMemsetAsync(bits.p, 0, bits.bytes, st));
+        launch_numord_mark(src, width, present, s->max_doc, s->n_pad, m->vmin, span, bits.as<uint32_t>(), st);
+        launch_numord_rank_sums(bits.as<uint64_t>(), words, sums.as<uint32_t>(), st);
+        HIPX(hipGetLastError());
+        uint32_t nd = 0;
+        HIPX(hipMemcpyAsync(&nd, sums.as<uint32_t>() + chunks, 4, hipMemcpyDeviceToHost, st));
+        HIPX(hipStreamSynchronize(st));
+        require(nd <= cap, ESGPU_ERR_UNSUPPORTED, over);
+        ddict.alloc(c, std::max<size_t>(nd, 1) * 8);
+        launch_numord_rank_write(bits.as<uint64_t>(), words, sums.as<uint32_t>(), m->vmin, nd, base.as<uint32_t>(), ddict.as<int64_t>(), st);
+        launch_numord_encode_dense(src, width, present, s->max_doc, s->n_pad, m->vmin, span, bits.as<uint64_t>(), base.as<uint32_t>(),
+                                   view->values.as<uint32_t>(), st);
+        HIPX(hipGetLastError());
+        td->longs.resize(nd);
+        if (nd) HIPX(hipMemcpyAsync(td->longs.data(), ddict.p, (size_t)nd * 8, hipMemcpyDeviceToHost, st));
+        HIPX(hipStreamSynchronize(st));
+    } else {
+        const uint64_t want = 2 * std::min<uint64_t>(cap, s->max_doc);
+        uint32_t slots = 1024;
+        while (slots < want) slots <<= 1;
+        const uint32_t probe_limit = std::min<uint32_t>(slots, 512);
+        const uint32_t out_cap = (uint32_t)std::min<uint64_t>(cap, s->max_doc);
+        const int64_t* v = (const int64_t*)wide_i64_locked(c, m, s, st);
+        DevBuf table, flags, out, rank;
+        table.alloc(c, (size_t)slots * 8);
+        flags.alloc(c, 16);  // sentinel seen, overflow, occupied slots
+        out.alloc(c, (size_t)out_cap * 8);
+        HIPX(hipMemsetAsync(table.p, 0xFF, table.bytes, st));
+        HIPX(hipMemsetAsync(flags.p, 0, flags.bytes, st));
+        launch_numord_hash_insert(v, present, s->max_doc, table.as<unsigned long long>(), slots, probe_limit, flags.as<uint32_t>(), st);
+        launch_numord_hash_compact(table.as<unsigned long long>(), slots, out_cap, out.as<int64_t>(), flags.as<uint32_t>() + 2, st);
+        HIPX(hipGetLastError());
+        uint32_t f[4] = {0, 0, 0, 0};
+        HIPX(hipMemcpyAsync(f, flags.p, 16, hipMemcpyDeviceToHost, st));
+        HIPX(hipStreamSynchronize(st));
+        const bool sentinel = f[kNumOrdFlagSentinel] != 0;
+        require(!f[kNumOrdFlagOverflow] && (uint64_t)f[2] + (sentinel ? 1 : 0) <= cap, ESGPU_ERR_UNSUPPORTED, over);
+        td->longs.resize(f[2]);
+        if (f[2]) HIPX(hipMemcpy(td->longs.data(), out.p, (size_t)f[2] * 8, hipMemcpyDeviceToHost));
+        if (sentinel) td->longs.push_back(-1);
+        std::sort(td->longs.begin(), td->longs.end());
+        const uint32_t nd = (uint32_t)td->longs.size();
+        out.release();
+        ddict.alloc(c, std::max<size_t>(nd, 1) * 8);
+        rank.alloc(c, (size_t)slots * 4);
+        if (nd) HIPX(hipMemcpyAsync(ddict.p, td->longs.data(), (size_t)nd * 8, hipMemcpyHostToDevice, st));
+        const uint32_t srank = sentinel ? (uint32_t)(std::lower_bound(td->longs.begin(), td->longs.end(), (int64_t)-1) - td->longs.begin())
+                                        : kMissingOrd;
+        launch_numord_hash_rank(table.as<unsigned long long>(), slots, ddict.as<int64_t>(), nd, rank.as<uint32_t>(), st);
+        launch_numord_encode_hash(v, present, s->max_doc, s->n_pad, table.as<unsigned long long>(), slots, probe_limit,
+                                  rank.as<uint32_t>(), srank, view->values.as<uint32_t>(), st);
+        HIPX(hipGetLastError());
+        HIPX(hipStreamSynchronize(st));
+    }
+    HIPX(hipStreamSynchronize(st));
+    td->n = td->longs.size();
+    td->seal();
+    view->value_count = td->n;
+    view->dict = std::move(td);
+    return view;
+}
+
+static DevColumn* ensure_num_ords(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st) {
+    DevColumn* m = const_cast<DevColumn*>(col);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!m->num_view) {
+        DevBuf ddict;
+        m->num_view = build_num_ords(c, m, s, st, ddict);
+        m->num_dict = std::move(ddict);
+    }
+    return m->num_view.get();
+}
+
+// the column a terms spec counts by: the keyword column itself, or a single-valued long column's numeric ordinals (built
+// on first use); null when the segment lacks the field
+static const DevColumn* terms_col_of(esgpu_ctx* c, const esgpu_segment* s, const char* field, hipStream_t st) {
+    const DevColumn* col = s->col(field);
+    if (!col || col->type == ESGPU_COL_ORD_U32) return col;
+    require(col->type != ESGPU_COL_F64, ESGPU_ERR_UNSUPPORTED, "terms over a double field (DoubleTerms) run on the CPU path");
+    require(col->type != ESGPU_COL_U64, ESGPU_ERR_UNSUPPORTED, "terms over an unsigned long field run on the CPU path");
+    require(!col->multi, ESGPU_ERR_UNSUPPORTED, "terms over a multi-valued long field run on the CPU path");
+    return ensure_num_ords(c, col, s, st);
+}
+static const DevColumn* terms_col(esgpu_plan* p, const esgpu_segment* s, const std::string& field) {
+    const DevColumn* col = terms_col_of(p->ctx, s, field.c_str(), p->stream);
+    if (col && col->dict && col->dict->numeric) p->long_fields.insert(field);
+    return col;
+}
+
 static void ensure_ord_hash(esgpu_ctx* c, const DevColumn* col, hipStream_t st) {
     DevColumn* mcol = const_cast<DevColumn*>(col);
     std::lock_guard<std::mutex> lk(c->mu);  // plans on different threads may share the segment
@@ -4265,6 +4422,10 @@ static Block terms_shell(const esgpu_plan* p, int spec, const std::vector<Block>
     r.min_doc_count = n.s.min_doc_count;
     r.order_path = n.order_path;
     r.show_err = n.s.show_term_doc_count_error;
+    if (p->long_fields.count(n.field)) {  // LongTerms: long keys beside their decimal text, the field's formatter
+        r.terms_kind = 1;
+        set_format(r, n);
+    }
     r.boff.assign(1, 0);
     r.term_off.assign(1, 0);
     for (const Block& b : protos) r.subs.push_back(b.like());
@@ -4290,6 +4451,17 @@ static void push_bucket(Block& b, int64_t key, const std::string* term, int64_t 
     b.term_off.push_back(b.term_pool.size());
     b.bcount.push_back(count);
     b.berr.push_back(0);
+}
+// a terms bucket: its ordinal in the producing shard, the term as the dictionary prints it and, for LongTerms, the long
+// itself from the numeric dictionary (d null: a plan without a dictionary numbers its terms)
+static void push_term_bucket(Block& b, const TermDict* d, uint64_t ord, int64_t count) {
+    std::string scratch;
+    if (b.terms_kind == 1) {
+        require(d && d->numeric && ord < d->longs.size(), ESGPU_ERR_STATE, "long terms built without their numeric dictionary");
+        b.term_long.push_back(d->longs[ord]);
+    }
+    if (d) push_bucket(b, (int64_t)ord, d->view(ord, scratch), count);
+    else push_bucket(b, (int64_t)ord, std::string_view(scratch = std::to_string(ord)), count);
 }
 
 // the cardinality sketches of the given bucket cells, gathered to the host in that order (rows index like HostCells)
@@ -4606,7 +4778,7 @@ static void emit_deep(const esgpu_plan* p, const ChildSrc& kid, size_t base, siz
     begin_instance(yb, other);
     std::string scratch;
     for (const TermPick& tp : top) {
-        push_bucket(yb, tp.ord, C0.tdictB->view(tp.ord, scratch), tp.count);
+        push_term_bucket(yb, C0.tdictB.get(), tp.ord, tp.count);
         if (tp.count == 0) { for (Block& sb : yb.subs) sb.append_empty(); continue; }
         for (size_t gj = 0; gj < kid.dgrand.size(); ++gj)
             append_leaf(p, p->pipes[kid.dgrand[gj].pipe], kid.dgrand[gj].leaf, base + (size_t)tp.ord * stride, yb.subs[gj]);
@@ -4756,8 +4928,8 @@ static bool replay_compact(esgpu_plan* p, const ChildSrc& kid, const std::vector
     if (nbatch > kReplayMaxBatches || wb > (1u << kReplayBatchShift) || dyn_claim_on()) return false;
     // the inner dictionary: the first retained segment with both fields (every later one must number alike)
     for (const esgpu_plan::DeferredSeg& d : p->dsegs) {
-        const DevColumn* a = d.s->col(R0.ord_field.c_str());
-        const DevColumn* b = d.s->col(R0.ord_field2.c_str());
+        const DevColumn* a = terms_col(p, d.s, R0.ord_field);
+        const DevColumn* b = terms_col(p, d.s, R0.ord_field2);
         if (!a || !b) continue;
         if (!rr.db) { rr.da = a->ord_dict(); rr.db = b->ord_dict(); rr.vcB = b->ord_count(); }
         else require(same_dict(a->ord_dict(), rr.da) && same_dict(b->ord_dict(), rr.db), ESGPU_ERR_INVALID,
@@ -4802,8 +4974,8 @@ static bool replay_compact(esgpu_plan* p, const ChildSrc& kid, const std::vector
     HIPX(hipMemcpyAsync(meta + coff, cap.data(), (size_t)nbatch * 4, hipMemcpyHostToDevice, st));
     HIPX(hipMemsetAsync(meta + foff, 0, fbytes + 16, st));
     for (const esgpu_plan::DeferredSeg& d : p->dsegs) {
-        const DevColumn* a = d.s->col(R0.ord_field.c_str());
-        const DevColumn* b = d.s->col(R0.ord_field2.c_str());
+        const DevColumn* a = terms_col(p, d.s, R0.ord_field);
+        const DevColumn* b = terms_col(p, d.s, R0.ord_field2);
         if (!a || !b) continue;
         ReplayCompactParams C{};
         C.n_docs = d.s->max_doc;
@@ -4857,8 +5029,8 @@ static bool replay_hot(esgpu_plan* p, const ChildSrc& kid, const std::vector<Ter
     esgpu_ctx* c = p->ctx;
     hipStream_t st = p->stream;
     const esgpu_plan::DeferredSeg& d = p->dsegs[0];
-    const DevColumn* a = d.s->col(R0.ord_field.c_str());
-    const DevColumn* b = d.s->col(R0.ord_field2.c_str());
+    const DevColumn* a = terms_col(p, d.s, R0.ord_field);
+    const DevColumn* b = terms_col(p, d.s, R0.ord_field2);
     if (!a || !b || a->multi || b->multi || T_outer > 65535 || a->ord_count() > 65535 || b->ord_count() <= 65536) return false;
     const uint16_t* a16 = ensure_ord16(c, a, d.s, st);
     if (!a16) return false;
@@ -5281,8 +5453,7 @@ static Block build_terms_root(esgpu_plan* p, const Group& g) {
         p->sk_ords.clear();
         begin_instance(r, other);
         for (const TermPick& tp : top) {
-            const std::string term = plan_term(p, P0, tp.ord);
-            push_bucket(r, tp.ord, &term, tp.count);
+            push_term_bucket(r, P0.tdict.get(), tp.ord, tp.count);
             p->sk_ords.push_back(tp.ord);
             for (Block& sb : r.subs) sb.append_empty();
         }
@@ -5534,8 +5705,7 @@ static Block build_terms_root(esgpu_plan* p, const Group& g) {
     std::vector<int64_t> counts;
     begin_instance(r, other);
     for (uint32_t i = 0; i < k; ++i) {
-        const std::string term = plan_term(p, P0, top[i].ord);
-        push_bucket(r, top[i].ord, &term, top[i].count);
+        push_term_bucket(r, P0.tdict.get(), top[i].ord, top[i].count);
         if (top[i].count == 0) {  // bucketEmptyAggregations (a compacted child's row is empty too: appended above)
             for (size_t ki = 0; ki < g.kids.size(); ++ki) if (!fast[ki]) r.subs[ki].append_empty();
             continue;
@@ -5561,8 +5731,7 @@ static Block build_terms_root(esgpu_plan* p, const Group& g) {
                 begin_instance(sub, rs.other[i]);
                 for (size_t j = 0; j < rs.picks[i].size(); ++j) {
                     const TermPick& tp = rs.picks[i][j];
-                    const std::string term2 = B0.tdict2->term(tp.ord);
-                    push_bucket(sub, tp.ord, &term2, tp.count);
+                    push_term_bucket(sub, B0.tdict2.get(), tp.ord, tp.count);
                     if (tp.count == 0) { for (Block& sb : sub.subs) sb.append_empty(); continue; }
                     for (size_t gj = 0; gj < kid.rgrand.size(); ++gj)
                         append_leaf(p, p->pipes[kid.rgrand[gj].pipe], kid.rgrand[gj].leaf, rs.cell[i][j], sub.subs[gj]);
@@ -5583,8 +5752,7 @@ static Block build_terms_root(esgpu_plan* p, const Group& g) {
                 begin_instance(sub, other2);
                 uint32_t dj = kid.deep >= 0 && !deep_off[ki].empty() ? deep_off[ki][i] : 0;
                 for (const TermPick& tp : top2) {
-                    const std::string term2 = B0.tdict2->term(tp.ord);
-                    push_bucket(sub, tp.ord, &term2, tp.count);
+                    push_term_bucket(sub, B0.tdict2.get(), tp.ord, tp.count);
                     if (tp.count == 0) { for (Block& sb : sub.subs) sb.append_empty(); ++dj; continue; }
                     for (size_t gj = 0; gj < kid.grand.size(); ++gj)
                         append_leaf(p, p->pipes[kid.grand[gj].pipe], kid.grand[gj].leaf, row + tp.ord, sub.subs[gj]);
@@ -5757,7 +5925,7 @@ static Block build_hist_root(esgpu_plan* p, const Group& g) {
             }
             begin_instance(sub, other);
             for (auto& tp : top) {
-                push_bucket(sub, tp.ord, B0.tdict->view(tp.ord, term_scratch), tp.count);
+                push_term_bucket(sub, B0.tdict.get(), tp.ord, tp.count);
                 if (tp.count == 0) { for (Block& sb : sub.subs) sb.append_empty(); continue; }
                 for (size_t gj = 0; gj < kid.grand.size(); ++gj)
                     append_leaf(p, p->pipes[kid.grand[gj].pipe], kid.grand[gj].leaf, row + tp.ord, sub.subs[gj]);
@@ -5847,8 +6015,10 @@ extern "C" int esgpu_plan_build(esgpu_plan* p, esgpu_result** out) {
                 // collected into the bucket, so GlobalOrdinalsStringTermsAggregator never set globalOrds and its
                 // buildAggregation returns buildEmptyAggregation() (GlobalOrdinalsStringTermsAggregator.java:147-149)
                 // -- with min_doc_count 0 it lists no zero-count terms.  The GPU plan's terms are always that
-                // aggregator (keyword fields through global ordinals: terms over numeric fields are refused at create);
-                // the map-mode StringTermsAggregator would instead list zero-count terms from every leaf (:110).
+                // aggregator for keyword fields (through global ordinals); the map-mode StringTermsAggregator would
+                // instead list zero-count terms from every leaf (:110), and so would LongTermsAggregator (:113-125):
+                // terms over a long field with min_doc_count 0 under a filter that matched no doc builds empty here
+                // too, a known difference from the reference.
                 if (dc == 0 && p->specs[g.root].s.type == ESGPU_AGG_TERMS) {
                     Block e = terms_shell(p, g.root, child_protos(p, g));
                     e.append_empty();
@@ -6198,8 +6368,7 @@ static Block colo_skeleton(esgpu_plan* tp, const unsigned long long* o, std::vec
     begin_instance(r, (int64_t)o[1]);
     for (uint64_t j = 0; j < o[0]; ++j) {
         const uint32_t ord = (uint32_t)o[2 + j];
-        const std::string term = plan_term(tp, P0, ord);
-        push_bucket(r, ord, &term, (int64_t)(o[2 + j] >> 32));
+        push_term_bucket(r, P0.tdict.get(), ord, (int64_t)(o[2 + j] >> 32));
         if (ords) ords->push_back(ord);
     }
     end_instance(r);
@@ -6407,8 +6576,7 @@ extern "C" int esgpu_plans_build_reduce(esgpu_plan* const* plans, int32_t n, esg
                     Block r = terms_shell(p, g.root, {});
                     begin_instance(r, other);
                     for (const TermPick& tp : top) {
-                        const std::string term = plan_term(p, P0, tp.ord);
-                        push_bucket(r, tp.ord, &term, tp.count);
+                        push_term_bucket(r, P0.tdict.get(), tp.ord, tp.count);
                         p->sk_ords.push_back(tp.ord);
                     }
                     end_instance(r);
@@ -6639,8 +6807,7 @@ static Block xr_reduce_terms(esgpu_plan* p0, const unsigned long long* recs, int
     out.doc_count_error.push_back(sumErr == -1 ? -1 : (S == 1 ? 0 : sumErr));
     out.other_doc_count.push_back(other);
     for (uint32_t i : keep) {
-        const std::string term = plan_term(p0, P0, ords[i]);
-        push_bucket(out, ords[i], &term, tcnt[i]);
+        push_term_bucket(out, P0.tdict.get(), ords[i], tcnt[i]);
         out.berr.back() = terr[i];
     }
     end_instance(out);

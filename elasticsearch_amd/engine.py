@@ -279,11 +279,13 @@ class Engine:
         N.check(N.lib().esgpu_ctx_hbm_used(self._ptr, ctypes.byref(v)))
         return v.value
 
-    OPTIONS = {"compact_columns": 1, "packed_metric": 2, "hll_floor": 3, "block_deltas": 4}  # include/esgpu.h ESGPU_OPT_*
+    OPTIONS = {"compact_columns": 1, "packed_metric": 2, "hll_floor": 3, "block_deltas": 4,
+               "numeric_terms_max_distinct": 5}  # include/esgpu.h ESGPU_OPT_*
 
     def set_option(self, name, value):
         """Layout option of this context (esgpu_ctx_set_option): 'compact_columns' / 'packed_metric' / 'block_deltas', 0 or 1;
-        'hll_floor' 0..8 (include/esgpu.h ESGPU_OPT_HLL_FLOOR)."""
+        'hll_floor' 0..8 (include/esgpu.h ESGPU_OPT_HLL_FLOOR); 'numeric_terms_max_distinct': the distinct values of a long field
+        in one segment above which terms over it are refused (default 2^22)."""
         N.check(N.lib().esgpu_ctx_set_option(self._ptr, self.OPTIONS[name], int(value)))
 
     def get_option(self, name):

@@ -82,8 +82,15 @@ int esgpu_device_count(int* count);
  *                              registers left below the floor are finished by the tail pass)
  *   ESGPU_OPT_BLOCK_DELTAS:    a dense time-sorted key column whose every run of 2,048 docs spans < 2^16 is read by
  *                              the raw-load collect kernels as 16-bit deltas over each run's minimum (2 B per doc
- *                              instead of 4; needs compact columns; ESGPU_B16=0 turns the default off) */
-enum { ESGPU_OPT_COMPACT_COLUMNS = 1, ESGPU_OPT_PACKED_METRIC = 2, ESGPU_OPT_HLL_FLOOR = 3, ESGPU_OPT_BLOCK_DELTAS = 4 };
+ *                              instead of 4; needs compact columns; ESGPU_B16=0 turns the default off)
+ * and one limit:
+ *   ESGPU_OPT_NUMERIC_TERMS_MAX_DISTINCT: terms over a long / date field count by the segment's numeric ordinals; a
+ *                              segment with more distinct values than this (default 2^22) is refused with
+ *                              ESGPU_ERR_UNSUPPORTED (its hash set holds twice as many slots) */
+enum {
+    ESGPU_OPT_COMPACT_COLUMNS = 1, ESGPU_OPT_PACKED_METRIC = 2, ESGPU_OPT_HLL_FLOOR = 3, ESGPU_OPT_BLOCK_DELTAS = 4,
+    ESGPU_OPT_NUMERIC_TERMS_MAX_DISTINCT = 5
+};
 int esgpu_ctx_set_option(esgpu_ctx* ctx, int32_t option, int64_t value);
 int esgpu_ctx_get_option(const esgpu_ctx* ctx, int32_t option, int64_t* value);
 
@@ -94,7 +101,10 @@ int esgpu_ctx_get_option(const esgpu_ctx* ctx, int32_t option, int64_t* value);
  * Column types (natural widths of SURVEY §8(d)):
  *   ESGPU_COL_ORD_U32 : SORTED / SORTED_SET doc values as u32 global ordinals, 0xFFFFFFFF = missing
  *                       (GlobalOrdinalsStringTermsAggregator.java:113-118; ord < 0 == missing)
- *   ESGPU_COL_I64     : SORTED_NUMERIC longs / dates as epoch millis (DateFieldMapper.java:539)
+ *   ESGPU_COL_I64     : SORTED_NUMERIC longs / dates as epoch millis (DateFieldMapper.java:539).  A terms aggregation
+ *                       over a single-valued one (LongTerms) counts by its numeric ordinals: each doc's rank among
+ *                       the segment's sorted distinct values, built on the device on first use and cached with the
+ *                       column.  Terms over a multi-valued long column, an F64 or a U64 column stay unsupported.
  *   ESGPU_COL_F64     : doubles (DoubleFieldMapper sortable-long already decoded to double)
  *   ESGPU_COL_U64     : murmur3 field hashes (Murmur3FieldMapper.java:160-162), stored as the signed long bits
  * Multi-valued columns are CSR: offsets[max_doc + 1] into values, values of one doc sorted ascending
@@ -173,7 +183,10 @@ int esgpu_segment_release_wide(esgpu_segment* seg, uint64_t* released);
  * Merges the segments' term dictionaries of `field` (each sorted by unsigned bytes, as Lucene stores them) into
  * global ordinals and remaps every segment's ordinal column on the GPU.  From then on, terms aggregations and
  * keyword term filters on these segments use global ordinals and resolve terms through the global dictionary
- * (until a segment is destroyed or remapped by another map).  Segments without the field are skipped. */
+ * (until a segment is destroyed or remapped by another map).  Segments without the field are skipped.
+ * A single-valued ESGPU_COL_I64 field is accepted too: each segment's numeric dictionary (its sorted distinct values)
+ * is built if need be, the dictionaries are merged on the host into the reader's, and every segment's numeric
+ * ordinals are remapped; esgpu_ordinal_map_value_count works, esgpu_ordinal_map_lookup returns ESGPU_ERR_INVALID. */
 typedef struct esgpu_ordinal_map esgpu_ordinal_map;
 int esgpu_ordinal_map_build(esgpu_ctx* ctx, esgpu_segment* const* segs, int32_t nsegs, const char* field,
                             esgpu_ordinal_map** out);
@@ -455,6 +468,9 @@ struct esgpu_agg_block {
     int32_t value_format;                   /* ESGPU_FORMAT_* */
     int32_t reserved_fmt;
     const char* format;                     /* pattern of DATE_TIME / NUMBER formats, else "" */
+    int32_t terms_kind;                     /* terms: 0 = StringTerms, 1 = LongTerms (a long / date field) */
+    int32_t reserved_kind;
+    const int64_t* term_longs;              /* [n_buckets] terms_kind 1: the bucket keys (term_bytes holds their decimal text) */
 };
 
 struct esgpu_result {
