@@ -29,9 +29,6 @@ constexpr uint32_t kGroup = kGroupBlocks;  // blocks per multi-pass group (esgpu
 #ifndef ESGPU_NBUF_NARROW  // load buffers in flight per thread for shapes reading one narrow column
 #define ESGPU_NBUF_NARROW 2  // measured: 4 no faster for terms(host), 4 % slower for date_histogram
 #endif
-#ifndef ESGPU_MINMAX_CHECK
-#define ESGPU_MINMAX_CHECK 1
-#endif
 #ifndef ESGPU_NBUF_COMPACT  // load buffers of the metric / two-dimension shapes over compact columns
 #define ESGPU_NBUF_COMPACT 2
 #endif
@@ -70,27 +67,12 @@ __device__ __forceinline__ uint32_t bits4(const uint64_t* bm, uint32_t doc0) {
     return (uint32_t)(bm[doc0 >> 6] >> (doc0 & 63)) & 0xFu;
 }
 
-// Column streams are read once per request: ESGPU_NT=1 marks them non-temporal (nt) so they do not displace the
-// cell grid and the zone maps in L2 / MALL.
-#ifndef ESGPU_NT
-#define ESGPU_NT 0
-#endif
+// Column streams are read once per request, with plain loads (marking them non-temporal, so that they would not displace
+// the cell grid and the zone maps in L2 / MALL, was tried and not kept).
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x4_t load16(const void* p) {
-#if ESGPU_NT
-    return __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
-#else
-    return *reinterpret_cast<const u32x4_t*>(p);
-#endif
-}
+__device__ __forceinline__ u32x4_t load16(const void* p) { return *reinterpret_cast<const u32x4_t*>(p); }
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u32x2_t load8(const void* p) {
-#if ESGPU_NT
-    return __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(p));
-#else
-    return *reinterpret_cast<const u32x2_t*>(p);
-#endif
-}
+__device__ __forceinline__ u32x2_t load8(const void* p) { return *reinterpret_cast<const u32x2_t*>(p); }
 __device__ __forceinline__ uint64_t join64(uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
 __device__ __forceinline__ void load_i64x4(const int64_t* p, uint32_t doc0, int64_t out[4]) {
     const u32x4_t a = load16(p + doc0), b = load16(p + doc0 + 2);
@@ -157,47 +139,26 @@ __device__ __forceinline__ uint32_t eval_pred(const PredDev& q, uint32_t doc0) {
 // timestamp column): loads only, no use of a loaded word until unpack_docs
 template <int MET, int VK, bool HIST>
 constexpr bool kRawPI = MET > 0 && (VK & 64) != 0 && (VK & 16) != 0 && (VK & 256) != 0 && (!HIST || (VK & (32 | 8192)) != 0);
-#ifndef ESGPU_B16_NOLOAD
-#define ESGPU_B16_NOLOAD 0
-#endif
-#ifndef ESGPU_B16_BRANCH  // single-key blocks skip the timestamp and base loads (a wave-uniform branch; with ESGPU_DOCS8
-#define ESGPU_B16_BRANCH 1  // measured level with the dummy loads on the north star, 3 % better on config 5)
-#endif
-#ifndef ESGPU_B16_SCALAR  // block-delta bases as scalar loads (1) or per-lane vector loads (0)
-#define ESGPU_B16_SCALAR 0
-#endif
 // VK bit 8192 (raw-load kernels only, instead of bit 32): the key column as block deltas -- 16 bits per doc over the
 // minimum of its run of 2^kB16Shift docs (one 8-byte word per run, the same for all 4 docs of a thread)
 constexpr uint32_t kNoUKey = 0xFFFFFFFFu, kOutUKey = 0xFFFFFFFEu;  // per-doc keys / one key outside the grid
 template <int VK>
 __device__ __forceinline__ void load_keys_raw(const CollectParams& P, uint32_t doc0, uint32_t (&raw)[11], uint32_t uk) {
     if constexpr ((VK & 8192) != 0) {
-        // a block whose docs all round to one key reads no timestamp: every lane loads the column's first word (one
-        // cache line per wave, in place of a branch around the load -- a load under a branch makes the compiler wait
-        // for the other buffers' loads)
-#if ESGPU_B16_NOLOAD  // timing experiment only (wrong keys in multi-key blocks): no timestamp or base loads at all
-        raw[2] = doc0; raw[3] = doc0; raw[4] = 0; raw[5] = 0; raw[10] = 0;
-        return;
-#endif
-#if ESGPU_B16_BRANCH  // (A/B) the single-key blocks' loads skipped under a wave-uniform branch
+        // a block whose docs all round to one key reads no timestamp and no base: the loads are skipped under a
+        // wave-uniform branch (against every lane loading the column's first word in place of the branch: level on the
+        // north star, 3 % better on config 5)
         if (uk != kNoUKey) {
             raw[2] = 0; raw[3] = 0; raw[4] = 0; raw[5] = 0; raw[10] = 0;
             return;
         }
-#endif
-        const u32x2_t t = load8(P.hv16 + (uk == kNoUKey ? doc0 : 0u));
+        const u32x2_t t = load8(P.hv16 + doc0);
         raw[2] = t.x; raw[3] = t.y;
         // bits 16..23 of the deltas (24-bit runs): the high-byte plane, or -- for a column whose every run spans < 2^16 --
         // the column's first word for all lanes (hv8_mask 0; the bytes are masked off by hv8_and = 0)
         raw[10] = *reinterpret_cast<const uint32_t*>(P.hv8 + (doc0 & P.hv8_mask));
-#if ESGPU_B16_SCALAR
-        // a wave's 256 docs lie in one run: its base is a scalar load
-        const int64_t b = P.hv16_base[__builtin_amdgcn_readfirstlane(doc0 >> kB16Shift)];
-        raw[4] = (uint32_t)b; raw[5] = (uint32_t)((uint64_t)b >> 32);
-#else
-        const u32x2_t b = load8(P.hv16_base + (doc0 >> kB16Shift));
+        const u32x2_t b = load8(P.hv16_base + (doc0 >> kB16Shift));  // the run's base, a per-lane vector load
         raw[4] = b.x; raw[5] = b.y;
-#endif
     } else {
         if constexpr ((VK & 16384) != 0) {  // single-key zone blocks read no 32-bit delta either (VK bit 16384)
             if (uk != kNoUKey) {
@@ -360,9 +321,6 @@ __device__ __forceinline__ void load_docs(const CollectParams& P, uint32_t doc0,
 #ifndef ESGPU_DOCS8_H  // ... the raw-load counting grids with a terms dimension (VK bit 1024; r5ab8: terms{date_histogram}
 #define ESGPU_DOCS8_H 1  // 0.96 -> 0.88 ms at 1B; the histogram-only grids measured 7 % slower at 8 and keep 4)
 #endif
-#ifndef ESGPU_B16_BRANCH8  // ... single-key blocks' timestamp loads skipped under a branch, else a dummy load (r5ab8:
-#define ESGPU_B16_BRANCH8 1  // north star 1.196 -> 1.165 ms)
-#endif
 struct Doc8 {
     Doc4 a, b;
 };
@@ -377,15 +335,13 @@ __device__ __forceinline__ void load_docs8(const CollectParams& P, uint32_t doc0
     }
     if constexpr (HIST) {
         if constexpr ((VK & 8192) != 0) {
-            bool skip = false;
-#if ESGPU_B16_BRANCH8
-            skip = uk != kNoUKey;  // a single-key block: no timestamp is read (wave-uniform branch)
-#endif
-            if (skip) {
+            // a single-key block: no timestamp is read (a wave-uniform branch; against a dummy load of the column's
+            // first word in its place, r5ab8: north star 1.196 -> 1.165 ms)
+            if (uk != kNoUKey) {
                 d.a.raw[2] = d.a.raw[3] = d.a.raw[4] = d.a.raw[5] = d.a.raw[10] = 0u;
                 d.b.raw[2] = d.b.raw[3] = d.b.raw[4] = d.b.raw[5] = d.b.raw[10] = 0u;
             } else {
-                const u32x4_t t = load16(P.hv16 + (uk == kNoUKey ? doc0 : 0u));
+                const u32x4_t t = load16(P.hv16 + doc0);
                 const u32x2_t bs = load8(P.hv16_base + (doc0 >> kB16Shift));  // (8 docs never straddle a run)
                 const u32x2_t h = load8(P.hv8 + (doc0 & P.hv8_mask));          // (see load_keys_raw)
                 d.a.raw[2] = t.x; d.a.raw[3] = t.y; d.b.raw[2] = t.z; d.b.raw[3] = t.w;
@@ -482,16 +438,10 @@ __device__ __forceinline__ void add_value(const Acc& a, uint32_t c, double x, bo
         const unsigned long long emn = nan ? 0ull : e;
         const unsigned long long emx = nan ? ~0ull : e;
         // read-check before the atomic: reads of one address broadcast, and min/max converge quickly
-        // (ESGPU_MINMAX_CHECK=0: unconditional no-return atomics -- no LDS read to wait on -- for A/B runs)
         constexpr uint32_t st = LDS ? MS : 1;
-#if ESGPU_MINMAX_CHECK
         const unsigned long long cmn = a.mn[c * st], cmx = a.mx[c * st];
         if (emn < cmn) atomicMin(&a.mn[c * st], emn);
         if (emx > cmx) atomicMax(&a.mx[c * st], emx);
-#else
-        atomicMin(&a.mn[c * st], emn);
-        atomicMax(&a.mx[c * st], emx);
-#endif
     }
     if (MET >= 3) {  // ExtendedStatsAggregator: sumOfSqr += value * value (no FMA)
         if (LDS) atomicAdd(&a.sq[ca], x * x);
@@ -664,22 +614,12 @@ __device__ __forceinline__ void run_flush(const CollectParams& P, const Acc& a, 
 // VK bit 4096 (with 2048): time-sorted data (a block's keys span less than one interval: CollectParams.runs1) -- one integer
 // run per thread, a third of the registers and no run lookup (config 2 at 1B docs: 1.46 -> 1.12 ms, r5d)
 // Integer runs over roughly time-ordered data (VK bit 2048 without 4096): the docs go to four window accumulators per
-// thread instead of three runs (ESGPU_WIN4=0: the runs, for A/B) -- see win_add
-#ifndef ESGPU_WIN4
-#define ESGPU_WIN4 1
-#endif
-template <int MET, int VK> constexpr bool kWin4 = ESGPU_WIN4 != 0 && MET > 0 && (VK & 2048) != 0 && (VK & 4096) == 0;
-#ifndef ESGPU_WIN_MK  // ... and the multi-key zone blocks of the one-run grids with single-key blocks (kWinMK): off --
-#define ESGPU_WIN_MK 0  // the accumulators' registers spill those kernels at 6 waves per SIMD (config 2 sorted 0.53 ->
-#endif                  // 3.66 ms with four slots, r6aw; 2.59 ms with two, r6ay)
-template <bool ORD, bool HIST, int MET, int VK>
-constexpr bool kWinMK = ESGPU_WIN_MK != 0 && !ORD && MET > 0 && (VK & 2048) != 0 && (VK & 4096) != 0 &&
-                        kUKeyK<ORD, HIST, MET, VK>;
-#ifndef ESGPU_WIN_MK_SLOTS  // key slots of the multi-key-block windows (kWinMK): 2 (an hour boundary inside a block)
-#define ESGPU_WIN_MK_SLOTS 2
-#endif
-template <bool ORD, bool HIST, int MET, int VK>
-constexpr int kWinSlots = kWinMK<ORD, HIST, MET, VK> ? ESGPU_WIN_MK_SLOTS : 4;
+// thread instead of three runs -- see win_add.  Tried and dropped: each doc straight into its key's LDS cells, in
+// lane-rotated copies -- config 2 at +-1 h jitter, 1B docs, 4.76 ms against 2.96 ms with the three runs, r6p: a wave's
+// docs land on ~3 keys and its f64 LDS atomics on those few addresses serialise; and the same windows for the multi-key
+// zone blocks of the one-run grids over sorted data -- the accumulators' registers spill those kernels at 6 waves per
+// SIMD, config 2 sorted 0.53 -> 3.66 ms with four slots, r6aw; 2.59 ms with two, r6ay.
+template <int MET, int VK> constexpr bool kWin4 = MET > 0 && (VK & 2048) != 0 && (VK & 4096) == 0;
 template <int MET, int VK = 0> constexpr int runs_for() {
     return MET == 0 ? 1 : (VK & 4096) != 0 ? 1 : kWin4<MET, VK> ? 1 : (VK & 2048) != 0 ? ESGPU_INT_RUNS_NR : ESGPU_RUNS;
 }
@@ -693,8 +633,8 @@ struct Runs {
     uint32_t victim;
     // packed integer cells (VK bit 64): the segment's most frequent ordinals (CollectParams.hot_t) accumulated in
     // registers for the current key slot -- the Zipf head's docs leave the LDS atomics, whose same-address conflicts they
-    // caused (ESGPU_PI_HOTU in the uniform-key path, ESGPU_PI_HOT per doc)
-    uint32_t hslot, hlo[kNHot], hhi[kNHot];
+    // caused (kPIHotU, in the uniform-key path)
+    uint32_t hslot;
     uint32_t hcnt[kNHot], hsum[kNHot];  // docs and their delta sum (a lane holds < 65,536 docs of a workgroup range)
     // window accumulators (kWin4): key slots wb .. wb + 3 -- per slot the docs, delta sum and squared-delta sum, and the
     // delta extrema as 16-bit pairs (slots 0/1 in wmn[0] / wmx[0], 2/3 in [1]); wb = kWinEmpty: none
@@ -719,50 +659,30 @@ __device__ __forceinline__ void runs_reset(Runs<NR>& R) {
     R.wmx[0] = R.wmx[1] = 0u;
 #pragma unroll
     for (int k = 0; k < kNHot; ++k) {
-        R.hlo[k] = ~0u;
-        R.hhi[k] = 0u;
         R.hcnt[k] = 0u;
         R.hsum[k] = 0u;
     }
 }
-#ifndef ESGPU_PI_HOT
-#define ESGPU_PI_HOT 0
-#endif
-#ifndef ESGPU_PI_MMCHECK  // packed cells: (min, max) pairs read first, atomics only where they change -- 2: one divergent
-                          // region per doc (NS 1.324 -> 1.29 ms, r5ab3), 1: one per bound, 0: unconditional (1.9x slower)
-#define ESGPU_PI_MMCHECK 2
-#endif
-#ifndef ESGPU_PI_NOATOM
-#define ESGPU_PI_NOATOM 0
-#endif
-#ifndef ESGPU_PI_STRAIGHT  // packed cells: straight-line reads and adds (1), or under the hit mask (0, for A/B runs)
-#define ESGPU_PI_STRAIGHT 1
-#endif
-// the hot ordinal's run into its LDS cell (before a window moves, and at the end)
-template <int MET, int NR>
+// the hot ordinal's run into its LDS cell (before a window moves, and at the end); its docs' (min, max) went to the cell
+// as they came (pi_uniform)
+template <int NR>
 __device__ __forceinline__ void pi_hot_flush(const CollectParams& P, const Acc& a, Runs<NR>& R, uint32_t T) {
 #pragma unroll
     for (int k = 0; k < kNHot; ++k) {
         if (R.hslot != ~0u && R.hcnt[k]) {
             const uint32_t c = R.hslot * T + P.hot_t[k];
             atomicAdd(&a.pk[c + a.coff], ((unsigned long long)R.hcnt[k] << P.pk_shift) + R.hsum[k]);
-            if (MET >= 2) {
-                if (R.hlo[k] < a.mm[2 * c]) atomicMin(&a.mm[2 * c], R.hlo[k]);
-                if (R.hhi[k] > a.mm[2 * c + 1]) atomicMax(&a.mm[2 * c + 1], R.hhi[k]);
-            }
         }
-        R.hlo[k] = ~0u;
-        R.hhi[k] = 0u;
         R.hcnt[k] = 0u;
         R.hsum[k] = 0u;
     }
     R.hslot = ~0u;
 }
 // the window accumulators into their LDS cells (each slot with docs as one integer run), then emptied
-template <int MET, int MS, int NR, int S = 4>
+template <int MET, int MS, int NR>
 __device__ __forceinline__ void win_flush(const CollectParams& P, const Acc& a, Runs<NR>& R) {
 #pragma unroll
-    for (int k = 0; k < S; ++k) {
+    for (int k = 0; k < 4; ++k) {
         if (R.wc[k]) {
             Run r;
             run_reset(r);
@@ -782,9 +702,9 @@ __device__ __forceinline__ void win_flush(const CollectParams& P, const Acc& a, 
     R.wmx[0] = R.wmx[1] = 0u;
     R.wb = kWinEmpty;
 }
-template <int MET, int MS, int NR, bool INT = false, bool WIN = false, int WS = 4>
+template <int MET, int MS, int NR, bool INT = false, bool WIN = false>
 __device__ __forceinline__ void runs_flush(const CollectParams& P, const Acc& a, Runs<NR>& R) {
-    if constexpr (WIN) win_flush<MET, MS, NR, WS>(P, a, R);
+    if constexpr (WIN) win_flush<MET, MS, NR>(P, a, R);
 #pragma unroll
     for (int k = 0; k < NR; ++k) {
         if constexpr (INT) run_flush_i<MET, MS>(P, a, R.r[k]);
@@ -851,12 +771,12 @@ __device__ __forceinline__ void runs_add_pk(const CollectParams& P, const Acc& a
 // one doc (v: it passes and has a key) into window slot o = slot - wb (o < 4 when v): the slot's 0/1 weight e multiplies
 // the delta into each sum (v_mad), so a doc costs ~30 VALU where the three runs' hit search and predicated updates took
 // ~110 (config 2 at ±1 h, SQ counters r6ac: 446 VALU per wave per 256 docs)
-template <int MET, int NR, int S = 4>
+template <int MET, int NR>
 __device__ __forceinline__ void win_add(Runs<NR>& R, uint32_t o, uint32_t x, bool v) {
     const uint32_t oh = v ? 1u << ((o & 3u) << 3) : 0u;  // one-hot byte of the slot
     const uint32_t xx = x * x;                              // (x < 2^16)
 #pragma unroll
-    for (int k = 0; k < S; ++k) {
+    for (int k = 0; k < 4; ++k) {
         const uint32_t e = (oh >> (8 * k)) & 0xFFu;
         R.wc[k] += e;
         R.ws[k] += x * e;
@@ -865,7 +785,7 @@ __device__ __forceinline__ void win_add(Runs<NR>& R, uint32_t o, uint32_t x, boo
     if (MET >= 2) {
         const uint32_t sh = (o & 1u) << 4;
         const uint32_t xm = (x << sh) | (0xFFFF0000u >> sh), xM = x << sh;  // the other half: min / max identities
-        const bool h0 = v && o < 2u, h1 = S > 2 && v && o >= 2u;
+        const bool h0 = v && o < 2u, h1 = v && o >= 2u;
         const u16x2_t m = __builtin_bit_cast(u16x2_t, xm), M = __builtin_bit_cast(u16x2_t, xM);
         const uint32_t n0 = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(u16x2_t, R.wmn[0]), m));
         const uint32_t n1 = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(u16x2_t, R.wmn[1]), m));
@@ -879,12 +799,11 @@ __device__ __forceinline__ void win_add(Runs<NR>& R, uint32_t o, uint32_t x, boo
 }
 // a doc whose slot is outside the window: flush it and re-base -- new keys above put the slot at the top (the keys of
 // roughly time-ordered data drift upwards), below at the bottom, a first doc one above the bottom
-template <int MET, int MS, int NR, int S = 4>
+template <int MET, int MS, int NR>
 __device__ __forceinline__ void win_rebase(const CollectParams& P, const Acc& a, Runs<NR>& R, uint32_t slot) {
     const uint32_t old = R.wb;
-    win_flush<MET, MS, NR, S>(P, a, R);
-    constexpr uint32_t top = S - 1;
-    R.wb = old == kWinEmpty ? (S > 2 && slot ? slot - 1u : slot) : slot > old ? (slot >= top ? slot - top : 0u) : slot;
+    win_flush<MET, MS, NR>(P, a, R);
+    R.wb = old == kWinEmpty ? (slot ? slot - 1u : slot) : slot > old ? (slot >= 3u ? slot - 3u : 0u) : slot;
 }
 template <int MET, int MS, int NR>
 __device__ __forceinline__ void runs_add(const CollectParams& P, const Acc& a, Runs<NR>& R, uint32_t slot, bool mpres, double x) {
@@ -921,73 +840,10 @@ __device__ __forceinline__ void runs_add(const CollectParams& P, const Acc& a, R
     }
 }
 
-// n docs at once into the run of `slot` (a thread's 4 docs that share a key slot, combined in registers first): the run
-// lookup and its predicated per-run updates once per 4 docs instead of once per doc
-template <int MET, int MS, int NR>
-__device__ __forceinline__ void runs_add_n(const CollectParams& P, const Acc& a, Runs<NR>& R, uint32_t slot, uint32_t n,
-                                           uint32_t vc, double sum, double sq, unsigned long long mn, unsigned long long mx) {
-    int hit = -1;
-#pragma unroll
-    for (int k = 0; k < NR; ++k) hit = R.r[k].slot == slot ? k : hit;
-    if (hit < 0) {
-        hit = NR == 1 ? 0 : (int)R.victim;
-#pragma unroll
-        for (int k = 0; k < NR; ++k)
-            if (k == hit) {
-                run_flush<MET, MS>(P, a, R.r[k]);
-                R.r[k].slot = slot;
-            }
-        if (NR > 1) R.victim = R.victim + 1 == (uint32_t)NR ? 0u : R.victim + 1;
-    }
-    // the hit run's fields selected into registers, updated once, and selected back (indexing R.r by `hit`, or
-    // updating under `k == hit`, lets the compiler turn the runs into a dynamically indexed array in scratch)
-    Run c = R.r[0];
-#pragma unroll
-    for (int k = 1; k < NR; ++k) {
-        const bool h = hit == k;
-        c.cnt = h ? R.r[k].cnt : c.cnt;
-        c.vc = h ? R.r[k].vc : c.vc;
-        c.sum = h ? R.r[k].sum : c.sum;
-        c.sq = h ? R.r[k].sq : c.sq;
-        c.mn = h ? R.r[k].mn : c.mn;
-        c.mx = h ? R.r[k].mx : c.mx;
-    }
-    c.cnt += n;
-    if (MET > 0) {
-        c.vc += vc;
-        c.sum += sum;
-        if (MET >= 3) c.sq += sq;
-        if (MET >= 2) {
-            c.mn = mn < c.mn ? mn : c.mn;
-            c.mx = mx > c.mx ? mx : c.mx;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-        const bool h = hit == k;
-        R.r[k].cnt = h ? c.cnt : R.r[k].cnt;
-        if (MET > 0) {
-            R.r[k].vc = h ? c.vc : R.r[k].vc;
-            R.r[k].sum = h ? c.sum : R.r[k].sum;
-            if (MET >= 3) R.r[k].sq = h ? c.sq : R.r[k].sq;
-            if (MET >= 2) {
-                R.r[k].mn = h ? c.mn : R.r[k].mn;
-                R.r[k].mx = h ? c.mx : R.r[k].mx;
-            }
-        }
-    }
-}
-#ifndef ESGPU_RUN4  // histogram-only grids: a thread's 4 docs with one key slot combined before the run update; measured
-#define ESGPU_RUN4 0  // slower (config 2 at 1B docs 2.15 -> 2.62 ms, date_histogram 1.03 -> 1.14 ms): off, kept for A/B
-#endif
-
-#ifndef ESGPU_ORDH_HOT  // counting ORD x histogram raw-load grids: the segment's most frequent ordinal counted in a
-#define ESGPU_ORDH_HOT 0  // register in single-key zone blocks (cnt_hot_flush), its docs off the LDS atomics -- measured
-#endif                    // slower (terms{date_histogram} 0.885 -> 1.046 ms at 1B, r6am): A/B option, off
-#ifndef ESGPU_COMBINE4  // counting ORD x histogram grids: combine a thread's equal keys before the LDS atomics
-#define ESGPU_COMBINE4 1
-#endif
-// calls emit(key, multiplicity) once per distinct key of k[0..3] (~0u = none)
+// counting ORD x histogram grids combine a thread's equal keys before the LDS atomics: calls emit(key, multiplicity)
+// once per distinct key of k[0..3] (~0u = none).  (Tried and dropped for the raw-load grids with single-key zone blocks:
+// the segment's most frequent ordinal counted in a register, its docs off the LDS atomics -- slower, terms{date_histogram}
+// 0.885 -> 1.046 ms at 1B, r6am.)
 template <class F>
 __device__ __forceinline__ void combine4(uint32_t (&k)[kVec], F emit) {
 #pragma unroll
@@ -1019,15 +875,6 @@ __device__ __forceinline__ void unpack_docs(const CollectParams& P, Doc4& d) {
     d.mpres = 0xFu;
 }
 
-// counting ORD x histogram raw-load grids with single-key zone blocks: the hot ordinal's register count (ESGPU_ORDH_HOT)
-template <bool ORD, bool HIST, int MET, int VK>
-constexpr bool kOrdHHot = ESGPU_ORDH_HOT != 0 && ORD && HIST && MET == 0 && kUKeyK<ORD, HIST, MET, VK>;
-template <int NR>
-__device__ __forceinline__ void cnt_hot_flush(const Acc& a, Runs<NR>& R, uint32_t T, uint32_t ht) {
-    if (R.hslot != ~0u && R.hcnt[0]) atomicAdd(&a.cnt32[R.hslot * T + ht + a.coff], R.hcnt[0]);
-    R.hcnt[0] = 0u;
-    R.hslot = ~0u;
-}
 template <bool ORD, bool HIST, int MET, bool LDS, bool KT, int MS, bool HORD = false, int VK = 0>
 __device__ __forceinline__ void process4(const CollectParams& P, const Acc& a, const Doc4& d_in, uint32_t T, int64_t base,
                                          uint32_t win0, Runs<runs_for<MET, VK>()>& run, uint32_t mw = 0, bool outer = true) {
@@ -1108,54 +955,25 @@ __device__ __forceinline__ void process4(const CollectParams& P, const Acc& a, c
             }
         }
     }
-    if constexpr (LDS && kIntRuns<ORD, MET, VK> && (VK & 4096) == 0) {
-        // roughly time-ordered data (the blocks span more than one key: no runs1): a thread's consecutive docs alternate
-        // between neighbouring keys and its three runs thrash -- each doc goes straight to its key's LDS cells instead,
-        // in the lane's rotated copy (CollectParams.hdirect, ncopies); the values are exact integers, so the cells'
-        // f64 sums equal the runs' (and the reference's sequential additions below 2^53)
-        if (P.hdirect) {
-#pragma unroll
-            for (int j = 0; j < kVec; ++j) {
-                if (!((d.ok >> j) & 1) || !hv_ok[j]) continue;
-                const uint32_t c = slot[j] + a.coff;
-                const double x = (double)(P.mv_base + (int64_t)d.mvd[j]);
-                atomicAdd(&a.cnt32[c], 1u);
-                atomicAdd(&a.sum[c], x);
-                if (MET >= 3) atomicAdd(&a.sq[c], x * x);
-                if (MET >= 2) {
-                    const unsigned long long e = sortable(x);
-                    if (e < a.mn[MS * slot[j]]) atomicMin(&a.mn[MS * slot[j]], e);
-                    if (e > a.mx[MS * slot[j]]) atomicMax(&a.mx[MS * slot[j]], e);
-                }
-            }
-            return;
-        }
-    }
-    // one-run grids over time-sorted data with single-key zone blocks (kWinMK): a multi-key block's quads (an hour
-    // boundary inside the block) go to the window accumulators too -- the one run flushed on every key change there, a
-    // wave's flushes on two LDS addresses
-    bool winq = kWin4<MET, VK>;
-    constexpr int WS = kWinSlots<ORD, HIST, MET, VK>;
-    if constexpr (kWinMK<ORD, HIST, MET, VK>) winq = !ublock;
-    if constexpr (LDS && kIntRuns<ORD, MET, VK> && (kWin4<MET, VK> || kWinMK<ORD, HIST, MET, VK>)) if (winq) {
+    if constexpr (LDS && kIntRuns<ORD, MET, VK> && kWin4<MET, VK>) {
         uint32_t vm = 0;
         bool miss = false;
 #pragma unroll
         for (int j = 0; j < kVec; ++j) {
             const bool v = ((d.ok >> j) & 1) && hv_ok[j];
             vm |= (uint32_t)v << j;
-            miss = miss || (v && slot[j] - run.wb >= (uint32_t)WS);
+            miss = miss || (v && slot[j] - run.wb >= 4u);
         }
         if (miss) {  // (rare: a lane's keys left its window) one doc at a time, re-basing where needed
 #pragma unroll
             for (int j = 0; j < kVec; ++j) {
                 if (!((vm >> j) & 1)) continue;
-                if (slot[j] - run.wb >= (uint32_t)WS) win_rebase<MET, MS, runs_for<MET, VK>(), WS>(P, a, run, slot[j]);
-                win_add<MET, runs_for<MET, VK>(), WS>(run, slot[j] - run.wb, d.mvd[j], true);
+                if (slot[j] - run.wb >= 4u) win_rebase<MET, MS, runs_for<MET, VK>()>(P, a, run, slot[j]);
+                win_add<MET, runs_for<MET, VK>()>(run, slot[j] - run.wb, d.mvd[j], true);
             }
         } else {
 #pragma unroll
-            for (int j = 0; j < kVec; ++j) win_add<MET, runs_for<MET, VK>(), WS>(run, slot[j] - run.wb, d.mvd[j], (vm >> j) & 1);
+            for (int j = 0; j < kVec; ++j) win_add<MET, runs_for<MET, VK>()>(run, slot[j] - run.wb, d.mvd[j], (vm >> j) & 1);
         }
         return;
     }
@@ -1182,53 +1000,8 @@ __device__ __forceinline__ void process4(const CollectParams& P, const Acc& a, c
         return;
     }
     if (LDS && !ORD) {  // ocnt_mode is OCNT_NONE without a terms dimension; without HIST the slot is always 0
-        if (ESGPU_RUN4) {
-            uint32_t okm = 0, first = ~0u;
-#pragma unroll
-            for (int j = 0; j < kVec; ++j) okm |= (((d.ok >> j) & 1) && hv_ok[j] ? 1u : 0u) << j;
-            bool same = true;
-#pragma unroll
-            for (int j = 0; j < kVec; ++j)
-                if ((okm >> j) & 1) {
-                    if (first == ~0u) first = slot[j];
-                    same = same && slot[j] == first;
-                }
-            // groups of docs with one key slot: all of them (time-sorted data: nearly always, a thread's 4 docs are
-            // consecutive), else one doc each; one run update per group (a rolled loop: one inlined copy of the update)
-            uint32_t rest = okm;
-#pragma unroll
-            for (int it = 0; it < kVec; ++it) {
-                if (!rest) break;
-                const uint32_t g = same ? rest : (rest & (0u - rest));
-                rest &= ~g;
-                uint32_t gs = first;
-#pragma unroll
-                for (int j = kVec - 1; j >= 0; --j)
-                    if (!same && ((g >> j) & 1)) gs = slot[j];
-                uint32_t vc = 0;
-                double sum = 0.0, sq = 0.0;
-                unsigned long long mn = kMinInit, mx = kMaxInit;
-                if (MET > 0) {
-#pragma unroll
-                    for (int j = 0; j < kVec; ++j) {
-                        const bool m = ((g >> j) & 1) && ((d.mpres >> j) & 1);
-                        const double x = m ? d.mv[j] : 0.0;
-                        vc += m ? 1u : 0u;
-                        sum += x;
-                        if (MET >= 3) sq += x * x;
-                        if (MET >= 2) {
-                            const bool nan = x != x;
-                            const unsigned long long e = sortable(x);
-                            const unsigned long long emn = !m ? kMinInit : nan ? 0ull : e, emx = !m ? kMaxInit : nan ? ~0ull : e;
-                            mn = emn < mn ? emn : mn;
-                            mx = emx > mx ? emx : mx;
-                        }
-                    }
-                }
-                runs_add_n<MET, MS>(P, a, run, gs, (uint32_t)__builtin_popcount(g), vc, sum, sq, mn, mx);
-            }
-            return;
-        }
+        // one run update per doc (a thread's 4 docs with one key slot combined before the update measured slower: config
+        // 2 at 1B docs 2.15 -> 2.62 ms, date_histogram 1.03 -> 1.14 ms)
 #pragma unroll
         for (int j = 0; j < kVec; ++j) {
             if (!((d.ok >> j) & 1) || !hv_ok[j]) continue;
@@ -1262,32 +1035,11 @@ __device__ __forceinline__ void process4(const CollectParams& P, const Acc& a, c
                 if (((d.ok >> j) & 1) && hv_ok[j]) atomicAdd(&a.ocnt32[slot[j]], 1u);
         }
         const unsigned long long one = 1ull << P.pk_shift;
-#if ESGPU_PI_HOT
-#pragma unroll
-        for (int j = 0; j < kVec; ++j) {
-            if (!((hit >> j) & 1) || d.ord[j] != P.hot_t[0]) continue;
-            if (slot[j] != run.hslot) {
-                pi_hot_flush<MET>(P, a, run, T);
-                run.hslot = slot[j];
-            }
-            run.hcnt[0] += 1u;
-            run.hsum[0] += d.mvd[j];
-            run.hlo[0] = min(run.hlo[0], d.mvd[j]);
-            run.hhi[0] = max(run.hhi[0], d.mvd[j]);
-            hit &= ~(1u << j);
-        }
-#endif
         // straight-line LDS traffic, so the compiler can count the one wait below (lgkmcnt(4): the reads, not the adds
         // queued behind them): every lane reads a (min, max) pair (a doc that hits nothing reads cell 0 and ignores it)
-        // and adds to a cell (a miss adds 0 to the lane's own spare word)
+        // and adds to a cell (a miss adds 0 to the lane's own spare word); with the reads and adds under the hit mask the
+        // compiler waits for every queued LDS op before the checks
         uint32_t mlo[kVec], mhi[kVec];
-#if ESGPU_PI_NOATOM  // diagnostic only (A/B builds; wrong results): no LDS cell traffic, the docs folded into registers
-#pragma unroll
-        for (int j = 0; j < kVec; ++j) run.hpk += ((hit >> j) & 1) ? one + d.mvd[j] + cell[j] : 0ull;
-        *a.pkd = run.hpk;
-        return;
-#endif
-#if ESGPU_PI_STRAIGHT
         if (MET >= 2) {
 #pragma unroll
             for (int j = 0; j < kVec; ++j) {
@@ -1301,44 +1053,10 @@ __device__ __forceinline__ void process4(const CollectParams& P, const Acc& a, c
             const bool h = (hit >> j) & 1;
             atomicAdd(h ? &a.pk[cell[j] + a.coff] : a.pkd, one + d.mvd[j]);  // (a miss: into the lane's spare word)
         }
-#else  // (A/B) reads and adds under the hit mask: the compiler then waits for every queued LDS op before the checks
         if (MET >= 2) {
-#pragma unroll
-            for (int j = 0; j < kVec; ++j) {
-                mlo[j] = 0u;
-                mhi[j] = ~0u;
-                if ((hit >> j) & 1) {
-                    const u32x2_t m = *reinterpret_cast<const u32x2_t*>(a.mm + 2 * cell[j]);
-                    mlo[j] = m.x;
-                    mhi[j] = m.y;
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < kVec; ++j)
-            if ((hit >> j) & 1) atomicAdd(&a.pk[cell[j] + a.coff], one + d.mvd[j]);
-#endif
-        if (MET >= 2) {
-#if ESGPU_PI_MMCHECK == 4
-            // one divergent loop over the lane's moving bounds (ESGPU_PI_MMU 4)
-            uint32_t need = 0;
-#pragma unroll
-            for (int j = 0; j < kVec; ++j)
-                need |= (uint32_t)(((hit >> j) & 1) && (d.mvd[j] < mlo[j] || d.mvd[j] > mhi[j])) << j;
-            while (need) {
-                const uint32_t j0 = (uint32_t)__builtin_ctz(need);
-                need &= need - 1u;
-                uint32_t c = 0, x = 0;
-#pragma unroll
-                for (int j = 0; j < kVec; ++j) {
-                    c = j0 == (uint32_t)j ? cell[j] : c;
-                    x = j0 == (uint32_t)j ? d.mvd[j] : x;
-                }
-                atomicMin(&a.mm[2 * c], x);
-                atomicMax(&a.mm[2 * c + 1], x);
-            }
-#elif ESGPU_PI_MMCHECK == 2
-            // one divergent region per doc: both atomics where either bound moves (the other is then a no-op)
+            // the pairs read above are the filter, atomics only where a bound moves -- one divergent region per doc, both
+            // atomics where either bound moves (the other is then a no-op): north star 1.324 -> 1.29 ms against one
+            // region per bound (r5ab3); unconditional atomics measured 1.9x slower
 #pragma unroll
             for (int j = 0; j < kVec; ++j) {
                 const bool mv = ((hit >> j) & 1) && (d.mvd[j] < mlo[j] || d.mvd[j] > mhi[j]);
@@ -1347,26 +1065,10 @@ __device__ __forceinline__ void process4(const CollectParams& P, const Acc& a, c
                     atomicMax(&a.mm[2 * cell[j] + 1], d.mvd[j]);
                 }
             }
-#elif ESGPU_PI_MMCHECK
-#pragma unroll
-            for (int j = 0; j < kVec; ++j) {
-                if (!((hit >> j) & 1)) continue;
-                if (d.mvd[j] < mlo[j]) atomicMin(&a.mm[2 * cell[j]], d.mvd[j]);
-                if (d.mvd[j] > mhi[j]) atomicMax(&a.mm[2 * cell[j] + 1], d.mvd[j]);
-            }
-#else  // (A/B) unconditional min / max atomics, a miss on the lane's spare word: no branches
-#pragma unroll
-            for (int j = 0; j < kVec; ++j) {
-                const bool h = (hit >> j) & 1;
-                uint32_t* w = h ? &a.mm[2 * cell[j]] : reinterpret_cast<uint32_t*>(a.pkd);
-                atomicMin(w, h ? d.mvd[j] : ~0u);
-                atomicMax(w + 1, h ? d.mvd[j] : 0u);
-            }
-#endif
         }
         return;
     }
-    if constexpr (LDS && ORD && HIST && MET == 0 && ESGPU_COMBINE4) if (P.ocnt_mode != OCNT_TERMS) {
+    if constexpr (LDS && ORD && HIST && MET == 0) if (P.ocnt_mode != OCNT_TERMS) {
         // counting grids: a thread's 4 docs usually share the outer key (time-sorted data) and often the cell (skewed
         // inner keys): equal keys are combined in registers, and an outer key shared by the whole wave takes one LDS
         // atomic for the wave instead of 64 on one address
@@ -1377,23 +1079,6 @@ __device__ __forceinline__ void process4(const CollectParams& P, const Acc& a, c
             const uint32_t t = d.ord[j];
             hk[j] = hit ? slot[j] : ~0u;
             cell[j] = hit && t != kMissingOrd && t < T ? slot[j] * T + t : ~0u;
-        }
-        if constexpr (kOrdHHot<ORD, HIST, MET, VK>) {
-            // a single-key zone block (wave-uniform): the hot ordinal's docs into the lane's register count for the key
-            // -- the Zipf head's same-address LDS atomics were the grid's conflicts
-            const uint32_t ht = P.hot_t[0];
-            if (ublock && ht < T) {
-                if (slot[0] != run.hslot) {
-                    cnt_hot_flush(a, run, T, ht);
-                    run.hslot = slot[0];
-                }
-#pragma unroll
-                for (int j = 0; j < kVec; ++j) {
-                    const bool h = cell[j] != ~0u && d.ord[j] == ht;
-                    run.hcnt[0] += h ? 1u : 0u;
-                    cell[j] = h ? ~0u : cell[j];
-                }
-            }
         }
         if (P.ocnt_mode == OCNT_HIST) {
             uint32_t key = ~0u, n = 0;
@@ -1436,22 +1121,11 @@ __device__ __forceinline__ void process4(const CollectParams& P, const Acc& a, c
 // takes this path for full blocks only), and the packed add's high word is a constant: pk_shift >= 33 (pi_fits: a
 // workgroup range holds < 2^31 docs), so `one + delta` is the pair {delta, one >> 32}.  NH = 1 or 2 Doc4 halves of one
 // step, processed together (their LDS reads issued before the adds).
-#ifndef ESGPU_PI_UFAST  // (A/B) 0: the general per-doc path for these blocks too
-#define ESGPU_PI_UFAST 1
-#endif
-#ifndef ESGPU_PI_HOTU  // the segment's most frequent ordinal counted and summed in registers in uniform blocks: 2 = with
-#define ESGPU_PI_HOTU 2  // (min, max) leaves only (north star 1.104 -> 1.046 ms at 1B, r6f: its LDS adds were the kernel's
-#endif                   // limit; avg grids, which are not LDS-bound, measured 5 % slower with it), 1 = always, 0 = never
-#ifndef ESGPU_PI_HOTMM  // (A/B) the hot ordinal's register run keeps its (min, max) too (no LDS read for its docs)
-#define ESGPU_PI_HOTMM 0  // (measured slower: north star 1.081 -> 1.133 ms at 1B, r6h -- its VALU cost; 2 or 3 hot ordinals 1.54 / 1.91)
-#endif
-#ifndef ESGPU_PI_HOTPK  // the hot ordinal's count and sum by packed 16-bit compares and v_dot2 (0: per-doc selects, A/B)
-#define ESGPU_PI_HOTPK 1
-#endif
-#ifndef ESGPU_PI_MMU  // (A/B) uniform blocks' (min, max) updates: 2 = one divergent region per doc (as ESGPU_PI_MMCHECK 2),
-#define ESGPU_PI_MMU 2  // 3 = branch-free -- every lane issues both atomics, lanes whose bounds do not move on a spare word;
-#endif                  // 4 = one divergent loop per lane over its moving bounds (north star 1.03 -> 1.06 ms, r6aj);
-                        // 5 = one region per pair of docs, four unconditional atomics (0.99-1.02 -> 1.03-1.04 ms, r6au)
+// The segment's most frequent ordinal is counted and summed in registers in these blocks where the grid has (min, max)
+// leaves (north star 1.104 -> 1.046 ms at 1B, r6f: its LDS adds were the kernel's limit); avg grids, which are not
+// LDS-bound, measured 5 % slower with it and go without.  (Tried and dropped: the register run keeping the hot ordinal's
+// (min, max) too -- north star 1.081 -> 1.133 ms at 1B, r6h, its VALU cost; 2 or 3 hot ordinals 1.54 / 1.91 ms.)
+template <int MET> constexpr bool kPIHotU = MET >= 2;
 template <int MET, int VK, int NH, int NR>
 __device__ __forceinline__ void pi_uniform(const CollectParams& P, const Acc& a, const Doc4& h0, const Doc4& h1, uint32_t T,
                                            uint32_t win0, Runs<NR>& run, uint32_t mw, bool outer) {
@@ -1493,13 +1167,12 @@ __device__ __forceinline__ void pi_uniform(const CollectParams& P, const Acc& a,
         hit[j] = (((okm >> j) & 1) != 0) & (t[j] < T);  // (a missing ordinal, 0xFFFF, is >= T)
         hpk[j] = hit[j];
     }
-    constexpr bool kHot = ESGPU_PI_HOTU == 1 || (ESGPU_PI_HOTU == 2 && MET >= 2);
-    if constexpr (kHot) {
+    if constexpr (kPIHotU<MET>) {
     if (sl != run.hslot) {  // (uniform) the hot ordinal's register run moves to this key
-        pi_hot_flush<MET>(P, a, run, T);
+        pi_hot_flush(P, a, run, T);
         run.hslot = sl;
     }
-    if constexpr (ESGPU_PI_HOTPK && NH == 1 && kNHot == 1 && !ESGPU_PI_HOTMM && (VK & 512) == 0) {
+    if constexpr (NH == 1 && kNHot == 1 && (VK & 512) == 0) {
         // packed: the hot ordinal's docs among the 4 found as zero 16-bit halves of (ordinals ^ hot), their count and
         // delta sum by v_dot2_u32_u16 (a doc equal to the hot ordinal is below T: no hit test needed without a bitset)
         // (no hot ordinal, kMissingOrd: 0xFFFE halves, which no 16-bit ordinal or missing value (0xFFFF) equals)
@@ -1517,23 +1190,16 @@ __device__ __forceinline__ void pi_uniform(const CollectParams& P, const Acc& a,
 #pragma unroll
         for (int k = 0; k < kNHot; ++k) {
             const uint32_t ht = P.hot_t[k];
-            uint32_t hc = run.hcnt[k], hs = run.hsum[k], hl = run.hlo[k], hh = run.hhi[k];
+            uint32_t hc = run.hcnt[k], hs = run.hsum[k];
 #pragma unroll
             for (int j = 0; j < N; ++j) {
                 const bool ho = hit[j] & (t[j] == ht);
                 hc += ho ? 1u : 0u;
                 hs += ho ? dv[j] : 0u;
-                if (MET >= 2 && ESGPU_PI_HOTMM) {  // ... and its extrema: the hot docs leave the (min, max) reads too
-                    hl = min(hl, ho ? dv[j] : ~0u);
-                    hh = max(hh, ho ? dv[j] : 0u);
-                    hit[j] = hit[j] & !ho;
-                }
                 hpk[j] = hpk[j] & !ho;
             }
             run.hcnt[k] = hc;
             run.hsum[k] = hs;
-            run.hlo[k] = hl;
-            run.hhi[k] = hh;
         }
     }
     }
@@ -1550,61 +1216,19 @@ __device__ __forceinline__ void pi_uniform(const CollectParams& P, const Acc& a,
     for (int j = 0; j < N; ++j)  // (a miss adds into the lane's spare word)
         atomicAdd(hpk[j] ? &a.pk[cb + t[j] + a.coff] : a.pkd, join64(dv[j], onehi));
     if (MET >= 2) {
-#if ESGPU_PI_MMU == 5
-        // one divergent region per pair of docs, its four atomics unconditional (a doc whose bounds stay on the lane's
-        // spare word)
-        uint32_t* spare = reinterpret_cast<uint32_t*>(a.pkd);
-#pragma unroll
-        for (int j = 0; j < N; j += 2) {
-            const bool m0 = hit[j] & ((dv[j] < mlo[j]) | (dv[j] > mhi[j]));
-            const bool m1 = hit[j + 1] & ((dv[j + 1] < mlo[j + 1]) | (dv[j + 1] > mhi[j + 1]));
-            if (m0 | m1) {
-                uint32_t* w0 = m0 ? &a.mm[2 * (cb + t[j])] : spare;
-                uint32_t* w1 = m1 ? &a.mm[2 * (cb + t[j + 1])] : spare;
-                atomicMin(w0, dv[j]);
-                atomicMax(w0 + 1, dv[j]);
-                atomicMin(w1, dv[j + 1]);
-                atomicMax(w1 + 1, dv[j + 1]);
-            }
-        }
-#elif ESGPU_PI_MMU == 4
-        // one divergent loop over the lane's moving bounds (most lanes have none: ~1 iteration where the per-doc regions
-        // issued the two atomics for up to N docs)
-        uint32_t need = 0;
-#pragma unroll
-        for (int j = 0; j < N; ++j) need |= (uint32_t)(hit[j] & ((dv[j] < mlo[j]) | (dv[j] > mhi[j]))) << j;
-        while (need) {
-            const uint32_t j0 = (uint32_t)__builtin_ctz(need);
-            need &= need - 1u;
-            uint32_t c = 0, x = 0;
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                c = j0 == (uint32_t)j ? t[j] : c;
-                x = j0 == (uint32_t)j ? dv[j] : x;
-            }
-            atomicMin(&a.mm[2 * (cb + c)], x);
-            atomicMax(&a.mm[2 * (cb + c) + 1], x);
-        }
-#elif ESGPU_PI_MMU == 3
-        uint32_t* spare = reinterpret_cast<uint32_t*>(a.pkd);
+        // one divergent region per doc, as in process4.  Tried and dropped: branch-free (every lane issues both atomics,
+        // lanes whose bounds do not move on a spare word); one divergent loop per lane over its moving bounds (north star
+        // 1.03 -> 1.06 ms, r6aj); one region per pair of docs with four unconditional atomics (0.99-1.02 -> 1.03-1.04
+        // ms, r6au)
 #pragma unroll
         for (int j = 0; j < N; ++j) {
-            const bool mv = hit[j] & ((dv[j] < mlo[j]) | (dv[j] > mhi[j]));
-            uint32_t* w = mv ? &a.mm[2 * (cb + t[j])] : spare;
-            atomicMin(w, dv[j]);
-            atomicMax(w + 1, dv[j]);
-        }
-#else
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            // (bitwise: one divergent region per doc -- a short-circuit && nests a second one around the comparisons)
+            // (bitwise: a short-circuit && nests a second divergent region around the comparisons)
             const bool mv = hit[j] & ((dv[j] < mlo[j]) | (dv[j] > mhi[j]));
             if (mv) {
                 atomicMin(&a.mm[2 * (cb + t[j])], dv[j]);
                 atomicMax(&a.mm[2 * (cb + t[j]) + 1], dv[j]);
             }
         }
-#endif
     }
 }
 
@@ -1800,15 +1424,15 @@ __global__ __launch_bounds__(WGS, (collect_min_waves<ORD, MET, VK, WGS>())) void
     g.coff = 0;
     g.ocnt64 = P.g_ocnt;
     g.pk = nullptr; g.mm = nullptr; g.pkd = nullptr;
-    // additive cell copies: grids with a terms dimension, and the per-doc integer-run grids (CollectParams.hdirect)
-    const uint32_t ncp = (ORD || (kIntRuns<ORD, MET, VK> && (VK & 4096) == 0)) ? max(P.ncopies, 1u) : 1u;
+    // additive cell copies: grids with a terms dimension
+    const uint32_t ncp = ORD ? max(P.ncopies, 1u) : 1u;
 
     // LDS window view.  Every pointer is derived from `smem` alone -- never merged with a global pointer -- so the
     // compiler keeps them in the LDS address space (ds_* instructions).  A generic pointer would compile to flat_*
     // accesses, and each flat load waits for vmcnt(0): the prefetched loads of the next iteration.
     constexpr bool PI = MET > 0 && (VK & 64) != 0;  // packed integer cells
     // ... over block-delta keys: full single-key zone blocks take pi_uniform
-    constexpr bool kPIU = ESGPU_PI_UFAST != 0 && PI && HIST && !HORD && kUKeyK<ORD, HIST, MET, VKL> && kRawPI<MET, VKL, HIST>;
+    constexpr bool kPIU = PI && HIST && !HORD && kUKeyK<ORD, HIST, MET, VKL> && kRawPI<MET, VKL, HIST>;
     Acc s;
     s.sum_lo = nullptr; s.sq_lo = nullptr;
     if constexpr (PI) {  // collect_lds_bytes(pi = true) mirrors this carve
@@ -1940,9 +1564,8 @@ __global__ __launch_bounds__(WGS, (collect_min_waves<ORD, MET, VK, WGS>())) void
     uint32_t pass = 0, npass = 1;                        // npass > 1: a multi-pass group
     auto slide_to = [&](uint32_t k0) {
         if (dirty) {
-            if (!ORD) runs_flush<MET, kMS, runs_for<MET, VKL>(), kIntRuns<ORD, MET, VKL>, kWin4<MET, VKL> || kWinMK<ORD, HIST, MET, VKL>, kWinSlots<ORD, HIST, MET, VKL>>(P, s, run);
-            if constexpr (PI && (ESGPU_PI_HOT != 0 || ESGPU_PI_HOTU != 0)) pi_hot_flush<MET>(P, s, run, T);
-            if constexpr (kOrdHHot<ORD, HIST, MET, VKL>) cnt_hot_flush(s, run, T, P.hot_t[0]);
+            if (!ORD) runs_flush<MET, kMS, runs_for<MET, VKL>(), kIntRuns<ORD, MET, VKL>, kWin4<MET, VKL>>(P, s, run);
+            if constexpr (PI && kPIHotU<MET>) pi_hot_flush(P, s, run, T);
             if constexpr (PI) flush_window_pi<MET, WGS>(P, s, T, W, win0, ncp);
             else flush_window<MET, kMS, WGS>(P, s, T, W, win0, ncp);
         }
@@ -2066,13 +1689,9 @@ __global__ __launch_bounds__(WGS, (collect_min_waves<ORD, MET, VK, WGS>())) void
             }
         }
     }
-#ifndef ESGPU_FLUSH_DIAG  // timing experiment only (wrong results): 1 = no final window flush
-#define ESGPU_FLUSH_DIAG 0
-#endif
-    if (P.lds_mode && (dirty || !(HIST && P.windowed)) && !ESGPU_FLUSH_DIAG) {
-        if (!ORD) runs_flush<MET, kMS, runs_for<MET, VKL>(), kIntRuns<ORD, MET, VKL>, kWin4<MET, VKL> || kWinMK<ORD, HIST, MET, VKL>, kWinSlots<ORD, HIST, MET, VKL>>(P, s, run);
-        if constexpr (PI && (ESGPU_PI_HOT != 0 || ESGPU_PI_HOTU != 0)) pi_hot_flush<MET>(P, s, run, T);
-        if constexpr (kOrdHHot<ORD, HIST, MET, VKL>) cnt_hot_flush(s, run, T, P.hot_t[0]);
+    if (P.lds_mode && (dirty || !(HIST && P.windowed))) {
+        if (!ORD) runs_flush<MET, kMS, runs_for<MET, VKL>(), kIntRuns<ORD, MET, VKL>, kWin4<MET, VKL>>(P, s, run);
+        if constexpr (PI && kPIHotU<MET>) pi_hot_flush(P, s, run, T);
         if constexpr (PI) flush_window_pi<MET, WGS>(P, s, T, W, win0, ncp);
         else flush_window<MET, kMS, WGS>(P, s, T, W, win0, ncp);
     }

@@ -89,12 +89,6 @@ __global__ void hc_init_kernel(HcParams P) {
 // A partition that receives more than 64 - pending offsets in one tile (clustered data) writes the excess straight to
 // memory from registers.  (Appending each tile's few offsets per partition to memory left lines partly written in L2:
 // WRITE_SIZE 3x the cold bytes; an LDS counting sort of the tile cost twice the LDS instructions of the ring.)
-#ifndef ESGPU_HC_NT
-#define ESGPU_HC_NT 1
-#endif
-#ifndef ESGPU_HC_EXP  // timing experiments only: 1 = classify alone (steps 2-5 and the flush skipped), 2 = loads alone
-#define ESGPU_HC_EXP 0
-#endif
 constexpr uint32_t kSeg = 32;
 constexpr uint32_t kRing = 2 * kSeg;
 constexpr uint32_t kCnt = (1u << 26) - 1u;  // word: ring base (0 or 32) << 26 | offsets since the last flush
@@ -166,12 +160,9 @@ __global__ __launch_bounds__(kHcWG) void hc_scatter_kernel(HcParams P) {
 #pragma unroll
         for (int k = 0; k < kHcIt; ++k) {
             const uint32_t d = min(t0 + k * (kHcWG * 4) + tid4, d_last);
-#if ESGPU_HC_NT  // the column is read once: non-temporal loads keep L2 for the partitions' open segments (5 % faster)
+            // the column is read once: non-temporal loads keep L2 for the partitions' open segments (5 % faster than plain)
             const u32x4_t a = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(P.rc + d));
             o[k][0] = a.x; o[k][1] = a.y; o[k][2] = a.z; o[k][3] = a.w;
-#else
-            load_u32x4(P.rc, d, o[k]);
-#endif
         }
     };
     auto process = [&](uint32_t t0, const uint32_t o[kHcIt][4]) {
@@ -195,15 +186,6 @@ __global__ __launch_bounds__(kHcWG) void hc_scatter_kernel(HcParams P) {
                 okm |= (((ok >> j) & 1u) && c ? 1u : 0u) << (k * 4 + j);
             }
         }
-#if ESGPU_HC_EXP == 2
-        {
-            uint32_t acc = 0;
-#pragma unroll
-            for (int d = 0; d < kD; ++d) acc += ((okm >> d) & 1u) ? o[d / 4][d % 4] : 0u;
-            if (acc == 0x12345678u) hot[0] = acc;
-            return;
-        }
-#endif
         // one LDS atomic per doc: a hot doc adds at its slot's counter (the 64 most frequent slots spread over 4 lane-
         // rotated copies), a cold doc at its partition's word and keeps the returned sequence number; one
         // ds_add_rtn_u32 with per-lane addresses serves both (two instructions cost twice: LDS atomics are issue-bound)
@@ -229,9 +211,6 @@ __global__ __launch_bounds__(kHcWG) void hc_scatter_kernel(HcParams P) {
             rk[d / 4][d % 4] = r;
         }
         const bool any_burst = __syncthreads_or(burst);
-#if ESGPU_HC_EXP == 1
-        return;
-#endif
         // 2. per partition: whole segments to flush (L), their destination, the ring state after the flush
         for (uint32_t p = threadIdx.x; p < P.P; p += kHcWG) {
             const uint32_t wd = word[p], C = wd & kCnt, rb = wd >> 26;
@@ -309,7 +288,7 @@ __global__ __launch_bounds__(kHcWG) void hc_scatter_kernel(HcParams P) {
     }
     __syncthreads();
     // the partitions' pending offsets (one partial segment); static-region fill; sentinel tail of an overflow chunk
-    for (uint32_t p = threadIdx.x; p < P.P && ESGPU_HC_EXP == 0; p += kHcWG) {
+    for (uint32_t p = threadIdx.x; p < P.P; p += kHcWG) {
         const HcPart q = P.part[p];
         const uint32_t wd = word[p], f = wd & kCnt, rb = wd >> 26;
         if (f) {

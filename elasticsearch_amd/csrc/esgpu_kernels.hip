@@ -953,10 +953,7 @@ bool launch_hll(const HllParams& p, uint32_t cus, hipStream_t st) {
     cuts.push_back(n);
     const uint32_t wgs_max = cus * 8;  // 8 workgroups of 256 threads per CU
     const bool fast = !p.accept && p.npred == 0 && !p.present;
-#ifndef ESGPU_HLL_LDS
-#define ESGPU_HLL_LDS 1
-#endif
-    const bool lds = ESGPU_HLL_LDS && fast && p.snap && (p.kind == HLL_I64 || p.kind == HLL_F64) && p.p >= 4;
+    const bool lds = fast && p.snap && (p.kind == HLL_I64 || p.kind == HLL_F64) && p.p >= 4;
     const uint32_t floor_grid = std::max(1u, std::min(64u, m / 4096));
     // floor (and group floors + LDS snapshot) of the registers as they stand
     auto refresh = [&]() {
@@ -1011,11 +1008,8 @@ bool launch_hll(const HllParams& p, uint32_t cus, hipStream_t st) {
     q.fs_f = 0;
     const bool warm = p.seen >= (uint64_t)m * cut0;  // the registers already passed the first cut
     if (warm && !p.snap_ok) refresh();
-#ifndef ESGPU_HLL_P0
-#define ESGPU_HLL_P0 1
-#endif
     // phase 0 partitioned by register range (the LDS phases' kinds, p >= 12: at least 64 ranges of whole groups)
-    const bool p0 = ESGPU_HLL_P0 && lds && !warm && p.p >= 12 && p.p0_cnt && cuts.size() > 1 && cuts[1] > 0;
+    const bool p0 = lds && !warm && p.p >= 12 && p.p0_cnt && cuts.size() > 1 && cuts[1] > 0;
     // LDS phases log their raises and a gather applies them (p.log_raises, set by the host when p0_cnt is there)
     const bool logr = lds && p.log_raises && p.p0_cnt && p.p >= 12;
     bool counted = false;  // the last launch that touched the registers was a gather: *nonzero is exact
@@ -3050,9 +3044,6 @@ void launch_comp_ords(const uint32_t* a, const uint32_t* b, uint32_t n_pad, uint
 // per batch -- and leave as one contiguous, coalesced run per batch after one global reservation per (workgroup, batch)
 // on its own cache line.  More batches: a position per wave round of each distinct batch, scattered appends.
 constexpr uint32_t kReplayFastBatches = 8;
-#ifndef ESGPU_RC_EXP  // timing experiments only (wrong results): 1 = no appends, 2 = no global reservations, 3 = loads alone
-#define ESGPU_RC_EXP 0
-#endif
 // the block's docs (16 per thread): each one's batch and replay ordinal (the slot map carries the batch: no per-doc
 // division); bid = kMissingOrd when the doc does not survive
 constexpr uint32_t kReplayLdsMap = 4096;  // outer ordinals whose slot map the sort kernel stages in LDS (16 KB)
@@ -3113,15 +3104,6 @@ __global__ __launch_bounds__(kWG, 2) void replay_compact_sort_kernel(ReplayCompa
     {
         uint32_t bid[kItersPerBlock][4];
         replay_classify(P, smap, val, bid);
-#if ESGPU_RC_EXP == 3
-        uint32_t acc = 0;
-#pragma unroll
-        for (int it = 0; it < kItersPerBlock; ++it)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc += val[it][j] + bid[it][j];
-        if (acc == 0x12345u) *P.overflow = acc;
-        return;
-#endif
 #pragma unroll
         for (int it = 0; it < kItersPerBlock; ++it)
 #pragma unroll
@@ -3163,11 +3145,7 @@ __global__ __launch_bounds__(kWG, 2) void replay_compact_sort_kernel(ReplayCompa
                 t += q == b ? x : 0u;
             }
         }
-#if ESGPU_RC_EXP == 2
-        const uint32_t g = blockIdx.x * 2048u;
-#else
         const uint32_t g = b < P.nbatch && t ? atomicAdd(&P.fill[(size_t)b * kReplayFillStride], t) : 0u;
-#endif
         const uint32_t cap = b < P.nbatch ? P.cap[b] : 0u;
         gdst[b] = (b < P.nbatch ? P.region[b] : 0ull) + g;  // where the batch's run goes, and how much of it fits
         glim[b] = cap > g ? cap - g : 0u;
@@ -3190,8 +3168,7 @@ __global__ __launch_bounds__(kWG, 2) void replay_compact_sort_kernel(ReplayCompa
         if (b < 4u) r[0] += 1ull << sh; else r[1] += 1ull << sh;
     }
     __syncthreads();
-    const uint32_t total = ESGPU_RC_EXP == 1 ? 0u : boff[kReplayFastBatches];
-    if (ESGPU_RC_EXP == 1 && threadIdx.x == 0 && stage[boff[1]] == 0x12345u) *P.overflow = 1u;
+    const uint32_t total = boff[kReplayFastBatches];
     for (uint32_t i = threadIdx.x; i < total; i += kWG) {
         uint32_t b = 0;
 #pragma unroll

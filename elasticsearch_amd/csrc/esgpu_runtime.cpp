@@ -1777,7 +1777,6 @@ static bool raw_hist_on();
 static bool dd_forced();
 static bool int_runs_on();
 static bool dot16_on();
-static uint32_t hdirect_copies();
 static bool runs1_on();
 static bool b16_on(const esgpu_ctx* c);
 static bool pi_cells(const esgpu_ctx* c);
@@ -1994,20 +1993,11 @@ static bool count_partitioned(esgpu_plan* p, Pipeline& pl, const uint32_t* ords,
 // them (GlobalOrdinalsBuilder.build via IndexFieldDataService's cache, C/index/fielddata/ordinals/
 // GlobalOrdinalsBuilder.java:46-70).
 // ------------------------------------------------------------------------------------------------------------
-#ifndef ESGPU_HOTCOLD
-#define ESGPU_HOTCOLD 1
-#endif
 #ifndef ESGPU_HOT_MAX
 #define ESGPU_HOT_MAX 16384  // hot slots at most (LDS counters of the scatter)
 #endif
 #ifndef ESGPU_HOT_PER_CU
 #define ESGPU_HOT_PER_CU 2  // hot-pass workgroups per CU (postings path; 4 measured 13 % slower)
-#endif
-#ifndef ESGPU_HC_POSTINGS
-#define ESGPU_HC_POSTINGS 1  // cold lists for requests without predicates / accept bits (0: always the scatter path)
-#endif
-#ifndef ESGPU_NO_HOT
-#define ESGPU_NO_HOT 0  // timing experiments: no hot set
 #endif
 
 // the postings hot pass reads the 16-bit hot-slot column (ESGPU_HOT16=0: the 32-bit recoded column, for A/B runs)
@@ -2151,7 +2141,7 @@ static std::shared_ptr<const HcStats> ensure_hc_stats(esgpu_ctx* c, const DevCol
         HIPX(hipMemcpyAsync(sel, K.sel, 8, hipMemcpyDeviceToHost, st));
         HIPX(hipMemcpyAsync(&total, K.out_sum, 8, hipMemcpyDeviceToHost, st));
         HIPX(hipStreamSynchronize(st));
-        if (H && !ESGPU_NO_HOT && sel[1]) {
+        if (H && sel[1]) {
             std::vector<unsigned long long> keys(sel[1]);
             HIPX(hipMemcpyAsync(keys.data(), dcand.p, keys.size() * 8, hipMemcpyDeviceToHost, st));
             HIPX(hipStreamSynchronize(st));
@@ -2259,7 +2249,7 @@ static std::shared_ptr<const HcStats> ensure_hc_stats(esgpu_ctx* c, const DevCol
         hs->d_rc.alloc(c, (size_t)s->n_pad * 4);
         launch_hc_recode((const uint32_t*)src, s->n_pad, dk.as<uint32_t>(), dv.as<uint32_t>(), log2, hs->d_rc.as<uint32_t>(), st);
         HIPX(hipGetLastError());
-        if (ESGPU_HC_POSTINGS && hc_hot16()) {  // slots < ESGPU_HOT_MAX (16,384) fit 16 bits beside the 0xFFFF sentinel
+        if (hc_hot16()) {  // slots < ESGPU_HOT_MAX (16,384) fit 16 bits beside the 0xFFFF sentinel
             hs->d_hot16.alloc(c, (size_t)s->n_pad * 2);
             launch_hc_hot16(hs->d_rc.as<uint32_t>(), s->n_pad, hs->d_hot16.as<uint16_t>(), st);
             HIPX(hipGetLastError());
@@ -2268,8 +2258,8 @@ static std::shared_ptr<const HcStats> ensure_hc_stats(esgpu_ctx* c, const DevCol
         HIPX(hipMemcpy(hs->d_hot_ord.p, hot.data(), hot.size() * 4, hipMemcpyHostToDevice));
         HIPX(hipStreamSynchronize(st));  // the table buffers are released on return
     }
-    if (ESGPU_HC_POSTINGS) {
-        // cold lists: the radix-partition passes over the recoded column (hot and missing values are >= T and skipped)
+    {
+        // cold lists (for requests without predicates / accept bits): the radix-partition passes over the recoded column (hot and missing values are >= T and skipped)
         // give the cold docs' offsets partition by partition; each partition's list is then copied to a 64-aligned start
         const uint32_t* col = hot.empty() ? (const uint32_t*)src : hs->d_rc.as<uint32_t>();
         std::vector<uint32_t> pad(P + 1, 0);
@@ -2958,19 +2948,7 @@ static bool collect_grid(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, co
 #ifndef ESGPU_TERMS_COPIES
 #define ESGPU_TERMS_COPIES 4
 #endif
-#ifndef ESGPU_COPIES_HIST
-#define ESGPU_COPIES_HIST 0  // terms x histogram grids: copies measured within noise
-#endif
-#ifndef ESGPU_ROW_TOPK
-#define ESGPU_ROW_TOPK 1  // terms under a histogram, count orders: per-row selection on the GPU at build
-#endif
-#ifndef ESGPU_FUSE_HIST_ORDS
-#define ESGPU_FUSE_HIST_ORDS 1  // histogram under histogram: inner key index derived in the collect kernel's loader
-#endif
 static constexpr uint32_t kTermsCopies = ESGPU_TERMS_COPIES;
-#ifndef ESGPU_COMPACT_ROWS
-#define ESGPU_COMPACT_ROWS 1  // build: histogram children of terms compacted on the GPU (0: host assembly, for A/B)
-#endif
 
 // cells of a terms-under-terms grid above which the inner buckets are collected breadth-first (ESGPU_DEFER_CELLS
 // overrides: tests force the replay on small grids)
@@ -3026,7 +3004,7 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
     // kernel, cardinality leaves) or the key span does not fit the loader's 32-bit division
     const DevColumn* osrc = pl.ord_hist && oc ? s->col(pl.ord_field.c_str()) : nullptr;
     int64_t ord_base = 0;
-    const bool fuse_ords = osrc && ESGPU_FUSE_HIST_ORDS && !multi && pl.cards.empty() && pl.ord_interval > 0 &&
+    const bool fuse_ords = osrc && !multi && pl.cards.empty() && pl.ord_interval > 0 &&
                            pl.ord_interval < (1ll << 32) && (uint64_t)pl.ord_keys * (uint64_t)pl.ord_interval < (1ull << 32) &&
                            !__builtin_mul_overflow(pl.ord_key0, pl.ord_interval, &ord_base) &&
                            !__builtin_add_overflow(ord_base, pl.ord_offset, &ord_base);
@@ -3254,9 +3232,6 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
         if (L_ORD && P.ord && plain_ord && !oc->multi && oc->ord_count() < 0xFFFFu) {
             P.ord16 = ensure_ord16(p->ctx, oc, s, p->stream);
             if (P.ord16) bytes_per_doc -= 2;
-            // counting terms x histogram grids: the hot ordinal the kernel counts in registers in single-key zone blocks
-            // (ESGPU_ORDH_HOT; the packed-cell grids take theirs below)
-            if (P.ord16 && L_HIST && L_met == 0) sampled_hot_ords(p->ctx, oc, s, P.hot_t);
         }
         if (L_HIST && hc && !pl.inner_terms && !P.kstart && hc->type == ESGPU_COL_I64 && !hc->multi && hc->vmin <= hc->vmax &&
             (uint64_t)hc->vmax - (uint64_t)hc->vmin < (1ull << 32)) {
@@ -3377,14 +3352,8 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
     // segment's blocks typically span more keys (90th percentile of the zone-map ranges), widen the window instead:
     // one 1024-thread workgroup per CU with up to kLdsMax of LDS (the same 16 waves per CU).
     bool wide = false;
-#ifndef ESGPU_WIDE_WINDOW
-#define ESGPU_WIDE_WINDOW 1
-#endif
-#ifndef ESGPU_WIDE_MIN  // widen to at least this many keys whenever the two-per-CU window is narrower (A/B knob)
-#define ESGPU_WIDE_MIN 0
-#endif
-    if (ESGPU_WIDE_WINDOW && P.lds_mode && P.windowed && !P.kstart && hc && pl.interval > 0) {
-        const int64_t need = std::min<int64_t>(std::max<int64_t>(hc->zspan / pl.interval + 2, ESGPU_WIDE_MIN), (int64_t)LH);
+    if (P.lds_mode && P.windowed && !P.kstart && hc && pl.interval > 0) {
+        const int64_t need = std::min<int64_t>(hc->zspan / pl.interval + 2, (int64_t)LH);
         if (need > (int64_t)W) {
             uint32_t w2 = W;
             while ((int64_t)w2 < need && collect_lds_bytes(LT, w2 + 1, L_met, L_vcnt, L_ocnt, 1, pi) <= kLdsMax) ++w2;
@@ -3398,9 +3367,10 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
     }
     P.W = W;
     // grids with a terms dimension: lane-rotated copies of the additive cells while they still fit two workgroups per
-    // CU (the Zipf-head terms otherwise serialise a wave's LDS atomics on one address)
+    // CU (the Zipf-head terms otherwise serialise a wave's LDS atomics on one address); not for terms x histogram grids,
+    // where copies measured within noise
     P.ncopies = 1;
-    if (P.lds_mode && L_ORD && (!L_HIST || ESGPU_COPIES_HIST)) {
+    if (P.lds_mode && L_ORD && !L_HIST) {
         for (uint32_t nc = kTermsCopies; nc > 1; nc /= 2) {
             const size_t b = collect_lds_bytes(LT, W, L_met, L_vcnt, L_ocnt, nc, pi);
             if (b <= kLdsPair) { P.ncopies = nc; lds = b; break; }
@@ -3423,7 +3393,7 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
         p->last_bytes += bytes_per_doc * (uint64_t)s->max_doc + (d_accept ? ((uint64_t)s->max_doc + 7) / 8 : 0);
         count_width(p, pl, s, true, first_segment);
         // (the hot/cold form keeps statistics per ordinal column: not for a column derived per request)
-        if (ESGPU_HOTCOLD && !pl.comp && collect_hotcold(p, pl, s, oc, d_accept, P.pred, P.npred, first_segment)) {
+        if (!pl.comp && collect_hotcold(p, pl, s, oc, d_accept, P.pred, P.npred, first_segment)) {
             if (first_segment) pl.zero_pending = false;  // (every counter stored, or never read: HcParams::overwrite)
             else zero_counts(p, pl);
             return 1;
@@ -3476,16 +3446,6 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
     // time-ordered data alternates between neighbouring keys and keeps three
     P.runs1 = m32 && P.mv16 && hc && pl.interval > 0 && hc->zspan < pl.interval && runs1_on() ? 1 : 0;
     P.dot16 = P.runs1 && mc && (uint64_t)mc->vmax - (uint64_t)mc->vmin <= 46340 && dot16_on() ? 1 : 0;
-    // ... and without runs1 (roughly time-ordered data), each doc straight into its key's LDS cells, in lane-rotated
-    // copies while they fit two workgroups per CU (ESGPU_HDIRECT=0: the three integer runs, for A/B runs)
-    P.hdirect = 0;
-    if (m32 && P.mv16 && !L_ORD && L_HIST && L_met > 0 && P.lds_mode && !P.runs1 && hdirect_copies() > 0) {
-        P.hdirect = 1;
-        for (uint32_t nc = hdirect_copies(); nc > 1; nc /= 2) {
-            const size_t b = collect_lds_bytes(LT, P.W, L_met, L_vcnt, L_ocnt, nc, pi);
-            if (b <= kLdsPair) { P.ncopies = nc; lds = b; break; }
-        }
-    }
     // raw-load kernels over 32-bit timestamp deltas (block deltas did not apply: runs spanning 2^16 ms or more) skip the
     // single-key zone blocks' deltas where most blocks hold one key (90 % of the blocks span less than one interval:
     // roughly time-ordered data displaced by minutes); with wider displacement the skip's conditional load costs more
@@ -3610,14 +3570,6 @@ static bool replay_compaction() {
     return on;
 }
 // integer run accumulators of histogram-only grids (VK bit 2048; ESGPU_INT_RUNS=0: the f64 runs, for A/B runs)
-// per-doc LDS cells for histogram-only integer-run grids over roughly time-ordered data (CollectParams.hdirect):
-// ESGPU_HDIRECT = the lane-rotated copies to try (0: off, the three integer runs).  Off: measured slower (config 2 at
-// +-1 h jitter, 1B docs: 2.96 ms with the runs, 4.76 ms with 2 or 4 copies, r6p -- the wave's docs land on ~3 keys, and
-// its f64 LDS atomics on those few addresses serialise)
-static uint32_t hdirect_copies() {
-    static const uint32_t n = [] { const char* e = std::getenv("ESGPU_HDIRECT"); return (uint32_t)(e && *e ? std::atoi(e) : 0); }();
-    return n;
-}
 // packed run updates for single-key zone blocks (CollectParams.dot16; ESGPU_DOT16=0: the unpacked update, for A/B runs)
 static bool dot16_on() {
     static const bool on = [] { const char* e = std::getenv("ESGPU_DOT16"); return !(e && *e == '0'); }();
@@ -5476,7 +5428,7 @@ static Block build_terms_root(esgpu_plan* p, const Group& g) {
         if (kid.filter) { for (int pi : kid.pipes) need_rows[pi] = 1; continue; }
         if (!kid.bucket) { need_rows[kid.leaf.pipe] = 1; continue; }
         const Pipeline& B0 = p->pipes[kid.pipes[0]];
-        bool ok = ESGPU_COMPACT_ROWS && B0.allocated && !B0.inner_terms && !B0.ord_hist && B0.cards.empty() &&
+        bool ok = B0.allocated && !B0.inner_terms && !B0.ord_hist && B0.cards.empty() &&
                   kid.grand.size() <= (size_t)kCompactLeaves && kid.deep < 0;
         for (const LeafRef& l : kid.grand) {  // the leaves' grids index like B0's (the kernel reads one cell of each)
             const Pipeline& L = p->pipes[l.pipe];
@@ -5814,7 +5766,7 @@ static Block build_hist_root(esgpu_plan* p, const Group& g) {
         const SpecNode& tn = p->specs[kid.spec];
         const bool count_order = tn.s.order == ESGPU_ORDER_COUNT_DESC || tn.s.order == ESGPU_ORDER_COUNT_ASC;
         const uint64_t S = std::min<uint64_t>(B0.value_count, (uint64_t)std::max<int64_t>(tn.s.shard_size, 0));
-        if (ESGPU_ROW_TOPK && !B0.ord_hist && B0.allocated && B0.tdict && count_order && B0.value_count == B0.T && S > 0 &&
+        if (!B0.ord_hist && B0.allocated && B0.tdict && count_order && B0.value_count == B0.T && S > 0 &&
             S <= kRowTopkMax) {
             pick_s[ki] = (uint32_t)S;
             B0.h_picks.ensure((size_t)B0.H * S * 8);
@@ -5829,7 +5781,7 @@ static Block build_hist_root(esgpu_plan* p, const Group& g) {
     }
     for (int pi : g.pipes) {
         Pipeline& pl = p->pipes[pi];
-        if (pl.allocated && (need[pi] || !pl.cards.empty() || !ESGPU_ROW_TOPK)) fetch_grid(p, pl);
+        if (pl.allocated && (need[pi] || !pl.cards.empty())) fetch_grid(p, pl);
     }
     bmark(p, "hist_issued");
     unsigned long long* ocnt = nullptr;
