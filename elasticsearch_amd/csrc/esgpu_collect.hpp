@@ -52,7 +52,7 @@ struct Doc4 {
     uint64_t racc;
     uint32_t doc0;
     // block-delta kernels (VK bit 8192): the grid key every doc of this buffer's zone block has (its zone-map range
-    // rounds to one key; kNoUKey: per-doc keys) -- the block's timestamps were then not read (zone_ukey)
+    // rounds to one key; kNoUKey: per-doc keys) -- the block's timestamps were then not read (z_take in collect_kernel)
     uint32_t ukey;
     uint32_t ord[kVec];
     int64_t hv[kVec];
@@ -194,7 +194,7 @@ constexpr bool kRawH = (VK & 1024) != 0;
 template <bool ORD, int MET, int VK>
 constexpr bool kIntRuns = !ORD && MET > 0 && (VK & 2048) != 0;
 // raw-load kernels whose key column is block deltas (VK bit 8192) or 32-bit deltas (bit 32): single-key zone blocks take
-// their key from the zone map (zone_ukey) and read no timestamp
+// their key from the zone map (z_take in collect_kernel) and read no timestamp
 template <bool ORD, bool HIST, int MET, int VK>
 constexpr bool kUKeyK = HIST && ((VK & 8192) != 0 || (VK & (32 | 16384)) == (32 | 16384)) &&
                         (kRawPI<MET, VK, HIST> || kRawH<ORD, MET, VK>);
@@ -627,6 +627,14 @@ template <int MET, int VK = 0> constexpr int runs_for() {
 #define ESGPU_PI_NHOT 1
 #endif
 constexpr int kNHot = ESGPU_PI_NHOT;
+// an LDS pointer as its 32-bit address and back (the pointers stay in the LDS address space: ds_* instructions)
+__device__ __forceinline__ uint32_t lds_addr(const void* p) {
+    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
+}
+template <class X>
+__device__ __forceinline__ X* lds_ptr(uint32_t addr) {
+    return (X*)(__attribute__((address_space(3))) X*)(uintptr_t)addr;
+}
 template <int NR>
 struct Runs {
     Run r[NR];
@@ -868,7 +876,7 @@ __device__ __forceinline__ void unpack_docs(const CollectParams& P, Doc4& d) {
     // is below 0xFFFF
     d.ord[0] = d.raw[0] & 0xFFFFu; d.ord[1] = d.raw[0] >> 16; d.ord[2] = d.raw[1] & 0xFFFFu; d.ord[3] = d.raw[1] >> 16;
     if constexpr (HIST) {
-        if (d.ukey == kNoUKey) unpack_keys_raw<VK>(P, d.raw, d.hv);  // (zone_ukey: kNoUKey on the other kernels)
+        if (d.ukey == kNoUKey) unpack_keys_raw<VK>(P, d.raw, d.hv);  // (z_take: kNoUKey on the other kernels)
         d.hpres = 0xFu;
     }
     d.mvd[0] = d.raw[6] & 0xFFFFu; d.mvd[1] = d.raw[6] >> 16; d.mvd[2] = d.raw[7] & 0xFFFFu; d.mvd[3] = d.raw[7] >> 16;
@@ -1130,7 +1138,7 @@ template <int MET, int VK, int NH, int NR>
 __device__ __forceinline__ void pi_uniform(const CollectParams& P, const Acc& a, const Doc4& h0, const Doc4& h1, uint32_t T,
                                            uint32_t win0, Runs<NR>& run, uint32_t mw, bool outer) {
     constexpr int N = 4 * NH;
-    const uint32_t k = h0.ukey;  // wave-uniform (zone_ukey: scalar loads)
+    const uint32_t k = h0.ukey;  // wave-uniform (z_take: scalar loads)
     const uint32_t sl = k - win0;
     const bool in = k < P.H && sl < (mw ? mw : P.W);
     uint32_t t[N], dv[N];
@@ -1178,8 +1186,10 @@ __device__ __forceinline__ void pi_uniform(const CollectParams& P, const Acc& a,
         // (no hot ordinal, kMissingOrd: 0xFFFE halves, which no 16-bit ordinal or missing value (0xFFFF) equals)
         const uint32_t ht = P.hot_t[0], htp = ht < T ? (ht | (ht << 16)) : 0xFFFEFFFEu;
         const u16x2_t one = {1, 1};
-        const u16x2_t e0 = one - __builtin_elementwise_min(__builtin_bit_cast(u16x2_t, h0.raw[0] ^ htp), one);
-        const u16x2_t e1 = one - __builtin_elementwise_min(__builtin_bit_cast(u16x2_t, h0.raw[1] ^ htp), one);
+        // 1 - x saturating at 0 is 1 for a zero half and 0 otherwise: one v_pk_sub_u16 with the clamp bit per pair of
+        // docs (one - min(x, one) compiled to a compare and a select per doc and a v_perm per pair)
+        const u16x2_t e0 = __builtin_elementwise_sub_sat(one, __builtin_bit_cast(u16x2_t, h0.raw[0] ^ htp));
+        const u16x2_t e1 = __builtin_elementwise_sub_sat(one, __builtin_bit_cast(u16x2_t, h0.raw[1] ^ htp));
         run.hcnt[0] = __builtin_amdgcn_udot2(e0, one, __builtin_amdgcn_udot2(e1, one, run.hcnt[0], false), false);
         run.hsum[0] = __builtin_amdgcn_udot2(e0, __builtin_bit_cast(u16x2_t, h0.raw[6]),
                                              __builtin_amdgcn_udot2(e1, __builtin_bit_cast(u16x2_t, h0.raw[7]), run.hsum[0], false),
@@ -1203,19 +1213,23 @@ __device__ __forceinline__ void pi_uniform(const CollectParams& P, const Acc& a,
         }
     }
     }
-    uint32_t mlo[N], mhi[N];
-    if (MET >= 2) {
+    if constexpr (MET >= 2) {
+        // one LDS address per doc: the packed word and the (min, max) pair are both 8 bytes per cell, so a hit doc's
+        // pair is at row + 8 * ordinal and its packed word a lane-constant distance from there; the pair's address is
+        // also where the bounds move, so the divergent regions compute no address
+        const uint32_t mm0 = lds_addr(a.mm), row = mm0 + 8u * cb;
+        const uint32_t dpk = lds_addr(a.pk + a.coff) - mm0;
+        uint32_t ca[N], mlo[N], mhi[N];
 #pragma unroll
         for (int j = 0; j < N; ++j) {  // (a doc that hits nothing reads cell 0: one broadcast address)
-            const u32x2_t m = *reinterpret_cast<const u32x2_t*>(hit[j] ? a.mm + 2 * (cb + t[j]) : a.mm);
+            ca[j] = hit[j] ? row + 8u * t[j] : mm0;
+            const u32x2_t m = *lds_ptr<u32x2_t>(ca[j]);
             mlo[j] = m.x;
             mhi[j] = m.y;
         }
-    }
 #pragma unroll
-    for (int j = 0; j < N; ++j)  // (a miss adds into the lane's spare word)
-        atomicAdd(hpk[j] ? &a.pk[cb + t[j] + a.coff] : a.pkd, join64(dv[j], onehi));
-    if (MET >= 2) {
+        for (int j = 0; j < N; ++j)  // (a miss adds into the lane's spare word; hpk implies hit)
+            atomicAdd(hpk[j] ? lds_ptr<unsigned long long>(ca[j] + dpk) : a.pkd, join64(dv[j], onehi));
         // one divergent region per doc, as in process4.  Tried and dropped: branch-free (every lane issues both atomics,
         // lanes whose bounds do not move on a spare word); one divergent loop per lane over its moving bounds (north star
         // 1.03 -> 1.06 ms, r6aj); one region per pair of docs with four unconditional atomics (0.99-1.02 -> 1.03-1.04
@@ -1225,10 +1239,14 @@ __device__ __forceinline__ void pi_uniform(const CollectParams& P, const Acc& a,
             // (bitwise: a short-circuit && nests a second divergent region around the comparisons)
             const bool mv = hit[j] & ((dv[j] < mlo[j]) | (dv[j] > mhi[j]));
             if (mv) {
-                atomicMin(&a.mm[2 * (cb + t[j])], dv[j]);
-                atomicMax(&a.mm[2 * (cb + t[j]) + 1], dv[j]);
+                atomicMin(lds_ptr<uint32_t>(ca[j]), dv[j]);
+                atomicMax(lds_ptr<uint32_t>(ca[j] + 4u), dv[j]);
             }
         }
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; ++j)  // (a miss adds into the lane's spare word)
+            atomicAdd(hpk[j] ? &a.pk[cb + t[j] + a.coff] : a.pkd, join64(dv[j], onehi));
     }
 }
 
@@ -1261,6 +1279,18 @@ __device__ void flush_window_pi(const CollectParams& P, const Acc& s, uint32_t T
         if (slot >= P.H) continue;
         const size_t g = (size_t)slot * T + t;
         const unsigned long long cnt = n >> sh;
+        // the cell's LDS words are read and reset before its global atomics are issued, and the reset pair is made
+        // here (kept across the loop it was spilled, and its reload -- a vector memory op queued behind the atomics --
+        // made every cell wait for its own atomics before the next cell's were issued)
+        uint32_t lo = 0, hi = 0;
+        if (MET >= 2) {
+            const u32x2_t m = *reinterpret_cast<const u32x2_t*>(s.mm + 2 * c);
+            lo = m.x;
+            hi = m.y;
+            u32x2_t r;
+            asm volatile("v_mov_b32 %0, -1\n\tv_mov_b32 %1, 0" : "=v"(r.x), "=v"(r.y));
+            *reinterpret_cast<u32x2_t*>(s.mm + 2 * c) = r;
+        }
         atomicAdd(&P.g_cnt[g], cnt);
         for (uint32_t k = 0; k < ncp; ++k) s.pk[k * C + c] = 0;
         // the cell's exact integer sum; compensated into the grid when its partial sums could pass 2^53
@@ -1273,11 +1303,8 @@ __device__ void flush_window_pi(const CollectParams& P, const Acc& s, uint32_t T
             atomicAdd(&P.g_sum[g], (double)isum);
         }
         if (MET >= 2) {
-            const uint32_t lo = s.mm[2 * c], hi = s.mm[2 * c + 1];
             atomicMin(&P.g_min[g], sortable((double)(P.mv_base + (int64_t)lo)));
             atomicMax(&P.g_max[g], sortable((double)(P.mv_base + (int64_t)hi)));
-            s.mm[2 * c] = ~0u;
-            s.mm[2 * c + 1] = 0u;
         }
     }
     if (P.ocnt_mode == OCNT_TERMS) {
@@ -1366,6 +1393,14 @@ __device__ __forceinline__ uint32_t claim_chunk(unsigned int* claim) {
     asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
     return atomicAdd(claim + zero, 1u);  // chunks claimed past the grid's first gridDim.x
 }
+
+// CollectParams.zkey as pairs (kmn, kmx) in the constant address space: the collect kernel also issues global atomics, so
+// through the plain pointer the compiler cannot take the array for unchanged and reads a wave-uniform word with a vector
+// load, whose vmcnt(0) wait drains every prefetched buffer; through this view the read is a scalar load (lgkmcnt).
+// Loads only -- nothing is written through it.
+typedef long long i64x2_t __attribute__((ext_vector_type(2)));
+typedef const i64x2_t __attribute__((address_space(4))) zkey_pair_c;
+__device__ __forceinline__ zkey_pair_c* zkey_view(const int64_t* zkey) { return (zkey_pair_c*)zkey; }
 
 // HK: 0 = no histogram dimension, 1 = affine rounding, 2 = bucket table (calendar units / DST zones)
 // WGS: threads per workgroup -- 512 (two resident per CU, each with an LDS window of <= 64 KB), or 1024 for
@@ -1536,19 +1571,48 @@ __global__ __launch_bounds__(WGS, (collect_min_waves<ORD, MET, VK, WGS>())) void
                          : (VK & 64) ? (ESGPU_NBUF_PI <= kItersPerBlockW ? ESGPU_NBUF_PI : kItersPerBlockW)
                          : ((VK & 176) ? (ESGPU_NBUF_COMPACT <= kItersPerBlockW ? ESGPU_NBUF_COMPACT : kItersPerBlockW) : 2);
     static_assert(kItersPerBlockW % kBuf == 0, "buffers per block");
-    // block-delta kernels: the zone block's key when all its docs share one (zone_keys ranges, two scalar loads per
-    // block and wave), the block's timestamps then left unread
-    auto zone_ukey = [&](uint32_t blk) -> uint32_t {
-        if constexpr (!kUKeyK<ORD, HIST, MET, VKL>) {
-            return kNoUKey;
-        } else {
-            const uint32_t b = __builtin_amdgcn_readfirstlane(blk);
-            const int64_t kmn = P.zkey[2 * b], kmx = P.zkey[2 * b + 1];
-            if (kmn != kmx) return kNoUKey;
-            return kmn >= 0 && kmn < (int64_t)P.H ? (uint32_t)kmn : kOutUKey;
+    // Zone-key ranges (P.zkey, written by zone_keys_kernel in an earlier launch: constant for this kernel) are read
+    // through zkey_view, one 16-byte scalar load per block.  A block's range is loaded a block ahead: when the prefetch
+    // enters block nb, z_issue names the block after nb on the schedule, behind that step's column loads; z_take takes
+    // the range when the prefetch enters that block (the block's single key for the loads, pf_uk, and its range
+    // [pf_mn, pf_mx]), and the window decision uses it when the block is processed, without a load of its own.  z_take
+    // reloads (and waits) if the block is not the one named ahead.  (These kernels keep ~75 scalars spilled to VGPR
+    // lanes, the loaded range among them, so an lgkmcnt(0) wait does follow the load -- behind the step's prefetch
+    // loads, where the wave next waits for its LDS reads anyway; what is gone is the vmcnt(0) that drained the buffers.)
+    const bool zk_on = HIST && (kUKeyK<ORD, HIST, MET, VKL> || (P.lds_mode != 0 && P.windowed != 0));
+    const zkey_pair_c* const zk = zkey_view(P.zkey);
+    uint32_t z_blk = ~0u;
+    i64x2_t z = {1, 0};
+    int64_t pf_mn = 1, pf_mx = 0;  // key range of the block the prefetches read (pf_blk); (1, 0): no key
+    uint32_t pf_uk = kNoUKey;      // ... and its key when all its docs share one (block-delta kernels: timestamps unread)
+    // ... in the grids with a terms dimension.  The histogram-only grids read a range where it is used (scalar loads too):
+    // their single-key blocks read no column at all, so there is no pipeline to drain and the carried scalars (spilled
+    // to VGPR lanes in these kernels) cost more than the waits -- at 1B docs, carried against read in place:
+    // date_histogram 0.593-0.597 against 0.567-0.570 ms, config 2 0.503-0.514 against 0.475-0.484 ms, config 2 at +-1 h
+    // 2.25-2.29 against 2.15-2.22 ms
+    constexpr bool kZCarry = ORD;
+    auto z_issue = [&](uint32_t blk) {
+        if constexpr (kZCarry) {
+            z_blk = blk;
+            z = zk[__builtin_amdgcn_readfirstlane(blk)];
         }
     };
-    uint32_t pf_blk = b_begin, pf_uk = zone_ukey(b_begin);  // the block the prefetches read, and its key
+    auto z_take = [&](uint32_t blk) {
+        pf_mn = z.x;
+        pf_mx = z.y;
+        if (!kZCarry || z_blk != blk) {
+            const i64x2_t c = zk[__builtin_amdgcn_readfirstlane(blk)];
+            pf_mn = c.x;
+            pf_mx = c.y;
+        }
+        if constexpr (kUKeyK<ORD, HIST, MET, VKL>)
+            pf_uk = pf_mn != pf_mx ? kNoUKey : pf_mn >= 0 && pf_mn < (int64_t)P.H ? (uint32_t)pf_mn : kOutUKey;
+    };
+    uint32_t pf_blk = b_begin;  // the block the prefetches read
+    if (zk_on) {
+        z_take(b_begin);
+        z_issue(min(b_begin + 1, b_end - 1));
+    }
     using Buf = std::conditional_t<WIDE8, Doc8, Doc4>;
     auto load_buf = [&](uint32_t doc0, Buf& d, uint32_t uk) {
         if constexpr (WIDE8) load_docs8<ORD, HIST, MET, VKL>(P, doc0, d, uk);
@@ -1576,9 +1640,9 @@ __global__ __launch_bounds__(WGS, (collect_min_waves<ORD, MET, VK, WGS>())) void
     };
     auto step = [&](uint32_t it, Buf& q) {
         if (it == 0) {
-            // ---- per-group / per-block decisions (wave-uniform: every lane reads the same zone-map words) ----
-            // readfirstlane: the zone-map words become scalar loads (lgkmcnt), not vector loads whose vmcnt wait
-            // would drain the prefetched buffers
+            // ---- per-group / per-block decisions (wave-uniform: every lane reads the same zone-key words) ----
+            // zkey_view with readfirstlane indices: scalar loads (lgkmcnt), not vector loads whose vmcnt wait would
+            // drain the prefetched buffers
             const uint32_t b = __builtin_amdgcn_readfirstlane(cb);
             if (cb == gb && pass == 0) {
                 if (dyn) {  // publish the pending claim (the chunk after this one), then claim the one after that
@@ -1592,8 +1656,14 @@ __global__ __launch_bounds__(WGS, (collect_min_waves<ORD, MET, VK, WGS>())) void
                 npass = 1;
                 if (use_lds && HIST && P.windowed) {
                     int64_t gmn = INT64_MAX, gmx = INT64_MIN, maxspan = 0;
-                    for (uint32_t x = b; x < ge; ++x) {
-                        const int64_t kmn = P.zkey[2 * x], kmx = P.zkey[2 * x + 1];
+                    // the group's ranges: kGroup scalar loads issued together, one wait (a short group reads its last
+                    // block again)
+                    i64x2_t zg[kGroup];
+#pragma unroll
+                    for (uint32_t x = 0; x < kGroup; ++x) zg[x] = zk[__builtin_amdgcn_readfirstlane(min(b + x, ge - 1))];
+#pragma unroll
+                    for (uint32_t x = 0; x < kGroup; ++x) {
+                        const int64_t kmn = zg[x].x, kmx = zg[x].y;
                         if (kmn > kmx) continue;  // no timestamp in the block
                         gmn = kmn < gmn ? kmn : gmn;
                         gmx = kmx > gmx ? kmx : gmx;
@@ -1613,7 +1683,14 @@ __global__ __launch_bounds__(WGS, (collect_min_waves<ORD, MET, VK, WGS>())) void
                 slide_to(win0 + W);
             }
             if (HIST && use_lds && P.windowed && npass == 1) {  // block by block: slide the window when it must
-                const int64_t kmn = P.zkey[2 * b], kmx = P.zkey[2 * b + 1];
+                // the block's range as the prefetch took it: at a block's first step every prefetch issued reads that
+                // block (pf_blk == cb; this step's own prefetch, below, is the first that can leave it)
+                int64_t kmn = pf_mn, kmx = pf_mx;
+                if constexpr (!kZCarry) {
+                    const i64x2_t c = zk[b];
+                    kmn = c.x;
+                    kmx = c.y;
+                }
                 if (kmn <= kmx) {
                     if (!win_set || kmn < (int64_t)win0 || kmx >= (int64_t)win0 + (int64_t)W) slide_to((uint32_t)kmn);
                 }
@@ -1662,11 +1739,28 @@ __global__ __launch_bounds__(WGS, (collect_min_waves<ORD, MET, VK, WGS>())) void
             else if (dyn && nb == ge) nb = nxt_c < P.n_chunks ? nxt_c * kGroup : cb;
             nb = min(nb, b_end - 1);
         }
+        bool z_next = false;
         if (nb != pf_blk) {
             pf_blk = nb;
-            pf_uk = zone_ukey(nb);
+            if (zk_on) {
+                z_take(nb);
+                z_next = true;
+            }
         }
         load_buf(nb * kBlockDocs + nit * kIterDocsW + tid4, q, pf_uk);
+        if (z_next) {
+            // the range of the block after nb, behind the step's loads: the next block; past the end of the group being
+            // processed, the group's first block when the pass that takes nb (the next one if the prefetch has wrapped:
+            // nb <= cb) is not the last, else the next group's or chunk's first.  (nb outside the group is the next
+            // group's first block, and a group has one block only as the range's last, where the bound below names it
+            // again.)
+            uint32_t zn = nb + 1;
+            if (nb >= gb && zn == ge) {
+                const uint32_t p = pass + (nb <= cb ? 1u : 0u);
+                zn = p + 1 < npass ? gb : dyn ? (nxt_c < P.n_chunks ? nxt_c * kGroup : nb) : ge;
+            }
+            z_issue(min(zn, b_end - 1));
+        }
     };
     while (cb < b_end) {
         for (uint32_t it = 0; it < (uint32_t)kItersPerBlockW; it += kBuf) {
@@ -1708,7 +1802,7 @@ __global__ __launch_bounds__(WGS, (collect_min_waves<ORD, MET, VK, WGS>())) void
 // the collect kernel's per-block window decisions are two scalar loads instead of two 64-bit divisions or table
 // searches per block); a block without values gets (1, 0)
 // udocs (optional): the docs of the blocks whose range rounds to one key, summed -- the block-delta kernels read no
-// timestamp of those blocks (zone_ukey), and the plan's byte count leaves them out
+// timestamp of those blocks (z_take in collect_kernel), and the plan's byte count leaves them out
 template <bool KT>
 __global__ __launch_bounds__(256) void zone_keys_kernel(CollectParams P, int64_t* __restrict__ out,
                                                         unsigned long long* __restrict__ udocs) {
