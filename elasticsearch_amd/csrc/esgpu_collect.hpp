@@ -627,6 +627,12 @@ template <int MET, int VK = 0> constexpr int runs_for() {
 #define ESGPU_PI_NHOT 1
 #endif
 constexpr int kNHot = ESGPU_PI_NHOT;
+// Ranked winner cells (VK bit 65536, CollectParams.rank_cells): the K x W cells of a ranked-terms collect leave LDS room
+// for many lane-rotated copies of the packed words, so the docs of a wave's Zipf-head terms no longer queue on one
+// address -- and the hot ordinal's register run, which existed to take those docs off the LDS, is dropped with its VALU
+// work (north star at 1B: 0.767 -> 0.700 ms without it).  (Tried and dropped: copies of the (min, max) pairs
+// too -- 0.733 -> 0.745 ms: the pair reads of one cell were a broadcast, the copies' reads are not.)
+template <int VK> constexpr bool kRankCells = (VK & 65536) != 0;
 // an LDS pointer as its 32-bit address and back (the pointers stay in the LDS address space: ds_* instructions)
 __device__ __forceinline__ uint32_t lds_addr(const void* p) {
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
@@ -1116,10 +1122,16 @@ __device__ __forceinline__ void process4(const CollectParams& P, const Acc& a, c
 #pragma unroll
     for (int j = 0; j < kVec; ++j) {
         if (!((d.ok >> j) & 1)) continue;
-        const uint32_t t = ORD ? d.ord[j] : 0u;
+        uint32_t t = ORD ? d.ord[j] : 0u, Tc = T;
         const bool has_t = ORD ? (t != kMissingOrd && t < T) : true;
+        if constexpr (ORD && !LDS) {  // ranked terms (a group of blocks on the global grid): rank -> the ordinal's column
+            if (P.rank_ord) {
+                Tc = P.T_full;
+                t = has_t ? P.rank_ord[t] : t;
+            }
+        }
         const double x = MET > 0 ? ((VK & 64) ? (double)(P.mv_base + (int64_t)d.mvd[j]) : d.mv[j]) : 0.0;
-        update_doc<ORD, HIST, MET, LDS, MS>(P, a, T, has_t, t, hv_ok[j], slot[j], MET > 0 && ((d.mpres >> j) & 1), x, outer);
+        update_doc<ORD, HIST, MET, LDS, MS>(P, a, Tc, has_t, t, hv_ok[j], slot[j], MET > 0 && ((d.mpres >> j) & 1), x, outer);
     }
 }
 
@@ -1133,7 +1145,7 @@ __device__ __forceinline__ void process4(const CollectParams& P, const Acc& a, c
 // leaves (north star 1.104 -> 1.046 ms at 1B, r6f: its LDS adds were the kernel's limit); avg grids, which are not
 // LDS-bound, measured 5 % slower with it and go without.  (Tried and dropped: the register run keeping the hot ordinal's
 // (min, max) too -- north star 1.081 -> 1.133 ms at 1B, r6h, its VALU cost; 2 or 3 hot ordinals 1.54 / 1.91 ms.)
-template <int MET> constexpr bool kPIHotU = MET >= 2;
+template <int MET, int VK = 0> constexpr bool kPIHotU = MET >= 2 && !kRankCells<VK>;
 template <int MET, int VK, int NH, int NR>
 __device__ __forceinline__ void pi_uniform(const CollectParams& P, const Acc& a, const Doc4& h0, const Doc4& h1, uint32_t T,
                                            uint32_t win0, Runs<NR>& run, uint32_t mw, bool outer) {
@@ -1175,7 +1187,7 @@ __device__ __forceinline__ void pi_uniform(const CollectParams& P, const Acc& a,
         hit[j] = (((okm >> j) & 1) != 0) & (t[j] < T);  // (a missing ordinal, 0xFFFF, is >= T)
         hpk[j] = hit[j];
     }
-    if constexpr (kPIHotU<MET>) {
+    if constexpr (kPIHotU<MET, VK>) {
     if (sl != run.hslot) {  // (uniform) the hot ordinal's register run moves to this key
         pi_hot_flush(P, a, run, T);
         run.hslot = sl;
@@ -1250,6 +1262,11 @@ __device__ __forceinline__ void pi_uniform(const CollectParams& P, const Acc& a,
     }
 }
 
+// the grid cell of LDS cell (key slot, t): column t of the row, or -- ranked terms -- the column of the ordinal with rank t
+__device__ __forceinline__ size_t grid_cell(const CollectParams& P, uint32_t slot, uint32_t T, uint32_t t) {
+    return P.rank_ord ? (size_t)slot * P.T_full + P.rank_ord[t] : (size_t)slot * T + t;
+}
+
 // packed integer cells (VK bit 64): decoded into the grid's u64 counts, f64 sums (the exact integer sum of the cell's
 // values, count * base + sum of deltas) and order-preserving extrema of (double) values -- (double) is monotonic on
 // longs, so the min / max of the casts are the casts of the min / max
@@ -1257,13 +1274,14 @@ template <int MET, int WGS>
 __device__ void flush_window_pi(const CollectParams& P, const Acc& s, uint32_t T, uint32_t W, uint32_t win0, uint32_t ncp) {
     __syncthreads();
     const uint32_t C = T * W;
+    const uint32_t CS = P.cstride ? P.cstride : C;  // distance between the copies
     const uint32_t sh = P.pk_shift;
     const unsigned long long mask = (1ull << sh) - 1ull;
     if (P.ocnt_mode == OCNT_TERMS_DERIVED) {
         for (uint32_t t = threadIdx.x; t < T; t += WGS) {
             unsigned long long tot = 0;
             for (uint32_t k = 0; k < ncp; ++k)
-                for (uint32_t l = 0; l < W; ++l) tot += s.pk[k * C + l * T + t];
+                for (uint32_t l = 0; l < W; ++l) tot += s.pk[k * CS + l * T + t];
             tot >>= sh;
             if (tot) atomicAdd(&P.g_ocnt[t], tot);
         }
@@ -1271,13 +1289,13 @@ __device__ void flush_window_pi(const CollectParams& P, const Acc& s, uint32_t T
     }
     for (uint32_t c = threadIdx.x; c < C; c += WGS) {
         unsigned long long n = 0;
-        for (uint32_t k = 0; k < ncp; ++k) n += s.pk[k * C + c];
+        for (uint32_t k = 0; k < ncp; ++k) n += s.pk[k * CS + c];
         if (n == 0) continue;
         const uint32_t local = c / T;
         const uint32_t t = c - local * T;
         const uint32_t slot = win0 + local;
         if (slot >= P.H) continue;
-        const size_t g = (size_t)slot * T + t;
+        const size_t g = grid_cell(P, slot, T, t);
         const unsigned long long cnt = n >> sh;
         // the cell's LDS words are read and reset before its global atomics are issued, and the reset pair is made
         // here (kept across the loop it was spilled, and its reload -- a vector memory op queued behind the atomics --
@@ -1292,7 +1310,7 @@ __device__ void flush_window_pi(const CollectParams& P, const Acc& s, uint32_t T
             *reinterpret_cast<u32x2_t*>(s.mm + 2 * c) = r;
         }
         atomicAdd(&P.g_cnt[g], cnt);
-        for (uint32_t k = 0; k < ncp; ++k) s.pk[k * C + c] = 0;
+        for (uint32_t k = 0; k < ncp; ++k) s.pk[k * CS + c] = 0;
         // the cell's exact integer sum; compensated into the grid when its partial sums could pass 2^53
         const long long isum = (long long)(n & mask) + (long long)cnt * P.mv_base;
         if (P.g_sum_lo) {
@@ -1343,7 +1361,7 @@ __device__ void flush_window(const CollectParams& P, const Acc& s, uint32_t T, u
         const uint32_t t = c - local * T;
         const uint32_t slot = win0 + local;
         if (slot >= P.H) continue;
-        const size_t g = (size_t)slot * T + t;
+        const size_t g = grid_cell(P, slot, T, t);
         atomicAdd(&P.g_cnt[g], (unsigned long long)n);
         for (uint32_t k = 0; k < ncp; ++k) s.cnt32[k * C + c] = 0;
         if (MET > 0) {
@@ -1476,9 +1494,10 @@ __global__ __launch_bounds__(WGS, (collect_min_waves<ORD, MET, VK, WGS>())) void
         s.cnt64 = nullptr; s.vcnt64 = nullptr; s.ocnt64 = nullptr;
         s.cnt32 = nullptr; s.vcnt32 = nullptr; s.sum = nullptr; s.sq = nullptr; s.mn = nullptr; s.mx = nullptr;
         s.mstride = 1;
-        s.pk = (unsigned long long*)carve(8 * C * ncp);
+        const uint32_t CS = P.cstride ? P.cstride : C;
+        s.pk = (unsigned long long*)carve(8 * CS * ncp);
         s.mm = (uint32_t*)carve(MET >= 2 ? 8 * C : 0);
-        s.coff = ((threadIdx.x & 63) % ncp) * C;
+        s.coff = ((threadIdx.x & 63) % ncp) * CS;
         s.ocnt32 = (uint32_t*)carve(P.ocnt_mode == OCNT_TERMS ? sizeof(uint32_t) * T
                                     : P.ocnt_mode == OCNT_HIST ? sizeof(uint32_t) * W : 0);
         s.pkd = (unsigned long long*)carve(8 * WGS) + threadIdx.x;
@@ -1499,7 +1518,7 @@ __global__ __launch_bounds__(WGS, (collect_min_waves<ORD, MET, VK, WGS>())) void
                                     : P.ocnt_mode == OCNT_HIST ? sizeof(uint32_t) * W : 0);
     }
     if (PI && P.lds_mode) {
-        for (uint32_t c = threadIdx.x; c < C * ncp; c += WGS) s.pk[c] = 0;
+        for (uint32_t c = threadIdx.x; c < (P.cstride ? P.cstride : C) * ncp; c += WGS) s.pk[c] = 0;
         if (MET >= 2)
             for (uint32_t c = threadIdx.x; c < C; c += WGS) { s.mm[2 * c] = ~0u; s.mm[2 * c + 1] = 0u; }
         if (P.ocnt_mode == OCNT_TERMS || P.ocnt_mode == OCNT_HIST)
@@ -1629,7 +1648,7 @@ __global__ __launch_bounds__(WGS, (collect_min_waves<ORD, MET, VK, WGS>())) void
     auto slide_to = [&](uint32_t k0) {
         if (dirty) {
             if (!ORD) runs_flush<MET, kMS, runs_for<MET, VKL>(), kIntRuns<ORD, MET, VKL>, kWin4<MET, VKL>>(P, s, run);
-            if constexpr (PI && kPIHotU<MET>) pi_hot_flush(P, s, run, T);
+            if constexpr (PI && kPIHotU<MET, VKL>) pi_hot_flush(P, s, run, T);
             if constexpr (PI) flush_window_pi<MET, WGS>(P, s, T, W, win0, ncp);
             else flush_window<MET, kMS, WGS>(P, s, T, W, win0, ncp);
         }
@@ -1785,7 +1804,7 @@ __global__ __launch_bounds__(WGS, (collect_min_waves<ORD, MET, VK, WGS>())) void
     }
     if (P.lds_mode && (dirty || !(HIST && P.windowed))) {
         if (!ORD) runs_flush<MET, kMS, runs_for<MET, VKL>(), kIntRuns<ORD, MET, VKL>, kWin4<MET, VKL>>(P, s, run);
-        if constexpr (PI && kPIHotU<MET>) pi_hot_flush(P, s, run, T);
+        if constexpr (PI && kPIHotU<MET, VKL>) pi_hot_flush(P, s, run, T);
         if constexpr (PI) flush_window_pi<MET, WGS>(P, s, T, W, win0, ncp);
         else flush_window<MET, kMS, WGS>(P, s, T, W, win0, ncp);
     }
@@ -1860,7 +1879,7 @@ static auto with_vk0(bool hv_f64, bool mv_f64, F f) {
 // over a long column.
 template <bool ORD, int HK, int MET, class F>
 static auto with_vk(bool hv_f64, bool mv_f64, bool dord, bool c16, bool t32, bool t16, bool pi, bool m32, bool m16, bool acc,
-                    bool raw, bool runs1, bool uk32, bool noc, F f) {
+                    bool raw, bool runs1, bool uk32, bool noc, bool rkc, F f) {
     // t16: the key column is read as block deltas (VK bit 8192 in place of 32) -- by the raw-load kernels only; the host
     // picks it only for a launch that takes one of them (t32 is then set as well)
     // VK bit 128, a compact long metric (u32 deltas, values restored in the loader): histogram-only grids over compact
@@ -1915,6 +1934,11 @@ static auto with_vk(bool hv_f64, bool mv_f64, bool dord, bool c16, bool t32, boo
             if constexpr (HK == 1) {
                 if (t32 && !hv_f64) {
                     // (+ bit 32768: the plan's outer counts are derived at the flush, none counted per doc)
+                    // (+ bit 65536: ranked winner cells, CollectParams.rank_cells -- stats leaves, unfiltered)
+                    if constexpr (MET == 2) {
+                        if (c16 && m16 && !acc && t16 && noc && rkc)
+                            return f(std::integral_constant<int, 65536 | 32768 | 16 | 8192 | 64 | 256>{});
+                    }
                     if (c16 && m16 && acc && t16 && noc) return f(std::integral_constant<int, 32768 | 16 | 8192 | 64 | 256 | 512>{});
                     if (c16 && m16 && t16 && noc) return f(std::integral_constant<int, 32768 | 16 | 8192 | 64 | 256>{});
                     if (c16 && m16 && acc && uk32 && noc) return f(std::integral_constant<int, 32768 | 16384 | 48 | 64 | 256 | 512>{});
@@ -1970,7 +1994,7 @@ static void launch_t(const CollectParams& p, bool wide, uint32_t grid, size_t ld
     with_vk<ORD, HK, MET>(p.hv_f64 != 0, p.mv_f64 != 0, p.ord_src != nullptr, p.ord16 != nullptr,
                           p.hv32 != nullptr || p.hv16 != nullptr, p.hv16 != nullptr, (p.mv32 || p.mv16) && p.pk_shift != 0, (p.mv32 || p.mv16) && p.pk_shift == 0, p.mv16 != nullptr,
                           p.accept != nullptr, p.raw_dense != 0, p.runs1 != 0, p.ukey32 != 0,
-                          p.ocnt_mode != OCNT_TERMS && p.ocnt_mode != OCNT_HIST, [&](auto vk) {
+                          p.ocnt_mode != OCNT_TERMS && p.ocnt_mode != OCNT_HIST, p.rank_cells != 0, [&](auto vk) {
         return with_wg<ORD, HK, MET>(wide, [&](auto wg) {
             hipLaunchKernelGGL((collect_kernel<ORD, HK, MET, decltype(vk)::value, decltype(wg)::value>), dim3(grid),
                                dim3(decltype(wg)::value), lds, st, p);
@@ -1994,7 +2018,7 @@ static int occ_t(size_t lds, int vkbits, bool wide) {
     return with_vk<ORD, HK, MET>((vkbits & 1) != 0, (vkbits & 2) != 0, (vkbits & 8) != 0, (vkbits & 16) != 0,
                                  (vkbits & (32 | 8192)) != 0, (vkbits & 8192) != 0, (vkbits & 64) != 0, (vkbits & 128) != 0, (vkbits & 256) != 0,
                                  (vkbits & 512) != 0, (vkbits & 1024) != 0, (vkbits & 4096) != 0, (vkbits & 16384) != 0,
-                                 (vkbits & 32768) != 0, [&](auto vk) {
+                                 (vkbits & 32768) != 0, (vkbits & 65536) != 0, [&](auto vk) {
         return with_wg<ORD, HK, MET>(wide, [&](auto wg) {
             int n = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(

@@ -125,12 +125,14 @@ int collect_occupancy(bool ord, int hk, int met, size_t lds, int vk, bool wide) 
 }
 
 
-size_t collect_lds_bytes(uint32_t T, uint32_t W, int met, int vcnt_mode, int ocnt_mode, uint32_t ncopies, bool pi) {
+size_t collect_lds_bytes(uint32_t T, uint32_t W, int met, int vcnt_mode, int ocnt_mode, uint32_t ncopies, bool pi,
+                         uint32_t cstride) {
     const size_t C = (size_t)T * W;
     const size_t n = std::max(ncopies, 1u);
     auto r = [](size_t b) { return (b + 15) & ~(size_t)15; };
     if (pi) {  // must match collect_kernel's carve order
-        size_t bytes = r(8 * C * n) + (met >= 2 ? r(8 * C) : 0);
+        const size_t CS = cstride ? (size_t)cstride : C;
+        size_t bytes = r(8 * CS * n) + (met >= 2 ? r(8 * C) : 0);
         if (ocnt_mode == OCNT_TERMS) bytes += r(4 * (size_t)T);
         if (ocnt_mode == OCNT_HIST) bytes += r(4 * (size_t)W);
         return bytes + 8 * 1024;  // a spare word per thread (1024-thread workgroups at most)
@@ -1693,6 +1695,15 @@ __global__ void pack_ord16_kernel(const uint32_t* src, uint32_t n, uint16_t* out
 }
 void launch_pack_ord16(const uint32_t* src, uint32_t n, uint16_t* out, hipStream_t st) {
     if (n) hipLaunchKernelGGL(pack_ord16_kernel, dim3(std::min<uint32_t>(8192, (n + 255) / 256)), dim3(256), 0, st, src, n, out);
+}
+__global__ void rank_ord16_kernel(const uint16_t* src, uint32_t n, const uint16_t* rank_of, uint32_t T, uint16_t* out) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const uint32_t o = src[i];
+        out[i] = o < T ? rank_of[o] : (uint16_t)0xFFFFu;
+    }
+}
+void launch_rank_ord16(const uint16_t* ord16, uint32_t n, const uint16_t* rank_of, uint32_t T, uint16_t* out, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(rank_ord16_kernel, dim3(std::min<uint32_t>(8192, (n + 255) / 256)), dim3(256), 0, st, ord16, n, rank_of, T, out);
 }
 __global__ void delta32_kernel(const int64_t* v, uint32_t n, int64_t base, uint32_t* out) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)

@@ -62,6 +62,15 @@ struct CollectParams {
     // terms dimension
     const uint32_t* ord;
     uint32_t T;
+    // ranked terms (collect path 10): ord16 holds each doc's frequency rank and T the ranks collected (the shard's top
+    // terms; larger ranks count as missing), while the grid keeps the segment's T_full ordinals per key -- a cell of rank r
+    // is flushed to column rank_ord[r] of its grid row.  rank_ord null: T counts ordinals and is the grid's row length
+    uint32_t T_full;
+    const uint32_t* rank_ord;
+    // packed cells: distance in cells between the lane-rotated copies of the count + sum words (0: T * W).  33 mod 64
+    // puts copy k of a cell 2k banks on, so the lanes of a wave that add to one cell use different banks
+    uint32_t cstride;
+    int32_t rank_cells;  // ranked winner cells (VK bit 65536): no hot-ordinal register run (the copies take its place)
     // compact columns (loader VK bits 16 / 32): the ordinals as u16 (0xFFFF missing), the histogram column's long values
     // as u32 deltas over hv_base (a missing value's delta is 0; hv_present still decides)
     const uint16_t* ord16;
@@ -352,7 +361,8 @@ void launch_collect(const CollectParams& p, bool ord, bool hist, int met, bool w
 // per-block key ranges of the zone maps under the request's rounding (out: 2 x n_blocks)
 void launch_zone_keys(const CollectParams& p, int64_t* out, hipStream_t s, unsigned long long* udocs = nullptr);
 // pi: packed integer metric cells (CollectParams.pk_shift): 8 B per cell copy + an 8 B (min, max) pair per cell
-size_t collect_lds_bytes(uint32_t T, uint32_t W, int met, int vcnt_mode, int ocnt_mode, uint32_t ncopies = 1, bool pi = false);
+size_t collect_lds_bytes(uint32_t T, uint32_t W, int met, int vcnt_mode, int ocnt_mode, uint32_t ncopies = 1, bool pi = false,
+                         uint32_t cstride = 0);  // cstride: CollectParams.cstride (packed cells)
 // resident workgroups per CU (hk: 0 none, 1 affine, 2 table; vk: bit 0 double histogram column, bit 1 double metric)
 int collect_occupancy(bool ord, int hk, int met, size_t lds, int vk, bool wide = false);
 // returns whether the group floors and snapshot are left as lower bounds of the registers (HllParams.snap_ok for the
@@ -412,6 +422,8 @@ void launch_minmax_i64(const int64_t* v, uint64_t n, int64_t* out, bool f64, hip
 void launch_widen_u32(const unsigned int* src, size_t n, unsigned long long* dst, hipStream_t st);
 void launch_narrow_u64(const unsigned long long* src, size_t n, unsigned int* dst, hipStream_t st);
 void launch_pack_ord16(const uint32_t* src, uint32_t n, uint16_t* out, hipStream_t st);
+// ranked terms: each doc's 16-bit ordinal replaced by its rank (rank_of[T] as u16; 0xFFFF stays missing)
+void launch_rank_ord16(const uint16_t* ord16, uint32_t n, const uint16_t* rank_of, uint32_t T, uint16_t* out, hipStream_t st);
 // ---- numeric ordinals (esgpu_numord.hip): a long column's sorted distinct values and each doc's rank among them ----
 // `v` with `width` 8 is the upload-width column, 4 / 2 its d32 / d16 deltas over vmin; span = vmax - vmin; the bitmap
 // holds span / 64 + 1 zeroed 64-bit words.  Spans below kNumOrdLdsBits are marked in a per-workgroup LDS bitmap.

@@ -37,6 +37,7 @@
 #include "../../include/esgpu.h"
 #include "es_common.hpp"
 #include "es_rounding.hpp"
+#include "es_term_rank.hpp"
 #include "esgpu_kernels.hpp"
 #include "esgpu_results.hpp"
 #include "esgpu_internal.hpp"
@@ -92,6 +93,7 @@ extern "C" int esgpu_ctx_set_option(esgpu_ctx* c, int32_t option, int64_t value)
         if (option == ESGPU_OPT_COMPACT_COLUMNS) c->opt_compact = (int)value;
         else if (option == ESGPU_OPT_PACKED_METRIC) c->opt_pi = (int)value;
         else if (option == ESGPU_OPT_BLOCK_DELTAS) c->opt_b16 = (int)value;
+        else if (option == ESGPU_OPT_RANKED_TERMS) c->opt_ranked = (int)value;
         else throw EsError(ESGPU_ERR_INVALID, "unknown context option");
     });
 }
@@ -103,6 +105,7 @@ extern "C" int esgpu_ctx_get_option(const esgpu_ctx* c, int32_t option, int64_t*
         else if (option == ESGPU_OPT_PACKED_METRIC) *value = c->opt_pi;
         else if (option == ESGPU_OPT_HLL_FLOOR) *value = c->opt_hll_fs;
         else if (option == ESGPU_OPT_BLOCK_DELTAS) *value = c->opt_b16;
+        else if (option == ESGPU_OPT_RANKED_TERMS) *value = c->opt_ranked;
         else if (option == ESGPU_OPT_NUMERIC_TERMS_MAX_DISTINCT) *value = c->opt_num_max;
         else throw EsError(ESGPU_ERR_INVALID, "unknown context option");
     });
@@ -305,6 +308,17 @@ static bool same_dict(const std::shared_ptr<const TermDict>& a, const std::share
 
 struct HcStats;  // hot set + partition capacities of a high-cardinality ordinal column (collect_hotcold)
 
+// Term counts and frequency ranks of a single-valued ordinal column with fewer than 65,535 terms (ensure_term_ranks,
+// DESIGN §5 "Ranked terms"): the segment's doc count per ordinal (immutable, Lucene's docFreq), the ordinals by count
+// descending (es_term_rank.hpp) and each doc's rank in 16 bits -- the column the ranked-terms collect reads in place of
+// the 16-bit ordinals (the same 2 B per doc)
+struct TermRanks {
+    uint32_t T = 0;
+    DevBuf counts;       // u64 [T]: doc count of every ordinal
+    DevBuf ord_of_rank;  // u32 [T]
+    DevBuf rank16;       // u16 [n_pad]: rank of the doc's ordinal, 0xFFFF missing
+};
+
 struct DevColumn {
     std::string name;
     int32_t type = 0;
@@ -352,6 +366,8 @@ struct DevColumn {
     // the most frequent ordinal of ords() in a sample (a hint for the packed cells' register run; any value is correct)
     uint32_t hot_ord[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
     const void* hot_src = nullptr;
+    std::unique_ptr<TermRanks> ranks;  // built on first use over values (no ordinal map), cached with the column
+    bool ranks_done = false;           // tried (ranks null: over the HBM budget)
     // numeric ordinals of a single-valued long column (ensure_num_ords, built on first use and cached with the column):
     // an ORD_U32 column over the segment's numeric dictionary -- the rank of each doc's value among the distinct values
     // of ALL the segment's docs -- which terms over the field count by like a keyword column (global ordinals included)
@@ -1073,6 +1089,10 @@ struct Pipeline {
     // number its terms the same way) -- shared, so it outlives the segments
     std::shared_ptr<const TermDict> tdict;
     bool fresh = true;               // no segment collected since create / reset: the grid shape is (re)derived
+    // ranked terms (collect path 10): the request's first segment was collected over its top-ranked terms only -- right
+    // while no second segment follows (ranked_live: the plan retains the segment; esgpu_plan_collect_segment re-collects
+    // it on the unranked path when one does, and ranked_off then keeps this plan, which serves one shard, off the path)
+    bool ranked_live = false, ranked_off = false;
     // timing of this pipeline's collect launch on the plan stream
     hipEvent_t e0 = nullptr, e1 = nullptr;
     bool timed = false;
@@ -1781,7 +1801,16 @@ static bool runs1_on();
 static bool b16_on(const esgpu_ctx* c);
 static bool pi_cells(const esgpu_ctx* c);
 static uint32_t pi_copies(int met);
+// ranked terms: the largest shard_size collected over ranks (K x W cells in LDS) -- covers the default shard_size of a
+// size-10 request over 10 or more shards (size x min(10, shards) = 100)
+constexpr uint32_t kRankedMax = 128;
+static uint32_t ranked_window();
+static uint32_t ranked_copies();
+static void clear_grid(esgpu_plan* p, Pipeline& pl);
 static const uint16_t* ensure_ord16(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
+static const TermRanks* ensure_term_ranks(esgpu_ctx* c, const DevColumn* col, const uint16_t* ord16, const esgpu_segment* s,
+                                          hipStream_t st);
+static bool ranked_terms_on(const esgpu_ctx* c);
 static const DevColumn* terms_col(esgpu_plan* p, const esgpu_segment* s, const std::string& field);
 static const uint32_t* ensure_d32(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
 static const uint16_t* ensure_d16(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
@@ -3327,11 +3356,45 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
 #define ESGPU_LDS_PI (52 * 1024)
 #endif
     const size_t kLdsPair = pi ? (size_t)ESGPU_LDS_PI : (size_t)ESGPU_LDS_PAIR, kLdsMax = 150 * 1024;
+    // Ranked terms: an unfiltered top-level terms aggregation in count order, alone in its shard's only
+    // segment, is settled by the segment's term counts before a doc is collected -- its top shard_size terms and every
+    // term's doc_count (the reference's breadth_first collect mode with the counting pass cached per segment).  The
+    // packed-cell window kernel then collects the sub-aggregations of those terms only: it reads each doc's frequency
+    // rank in place of its ordinal, ranks past shard_size count as missing, and the LDS cells are [W keys][K ranks]
+    // instead of [W][T].  The grid, the outer counts (copied from the cached counts) and the build are unchanged.
+    const TermRanks* rk = nullptr;
+    bool rkc = false;  // ... in ranked winner cells
+    uint32_t LK = LT;  // terms dimension of the LDS cells
+    auto b24_fits = [&] {
+        return t16 && (!t16->b16_hi.p || b24_mode() == 2 || (pl.interval > 0 && !P.kstart && hc->zspan < pl.interval));
+    };
+    P.rank_cells = 0;
+    if (pi && ranked_terms_on(p->ctx) && first_segment && !pl.ranked_off && terms_outer && L_HIST && hk_launch == 1 && P.ord16 &&
+        !inner_missing && pl.ocnt_mode == OCNT_TERMS_DERIVED && pl.cards.empty() && pl.fspec < 0 && !pl.comp && !pl.ord_hist &&
+        !oc->gdict && !oc->multi && oc->value_count >= 1 && p->filters.empty() && !d_accept && P.npred == 0 && !P.accept) {
+        const esgpu_agg_spec& ts = p->specs[pl.term_spec].s;
+        const bool no_replay = std::none_of(p->pipes.begin(), p->pipes.end(),
+                                            [](const Pipeline& x) { return x.replay || x.can_defer || x.deferred; });
+        if (ts.parent < 0 && ts.order == ESGPU_ORDER_COUNT_DESC && ts.min_doc_count >= 1 && ts.shard_size >= 1 &&
+            ts.shard_size <= (int32_t)kRankedMax && no_replay && (p->dsegs.empty() || p->dsegs[0].s == s))
+            rk = ensure_term_ranks(p->ctx, oc, P.ord16, s, p->stream);
+        if (rk) LK = std::min<uint32_t>((uint32_t)ts.shard_size, LT);
+    }
     uint32_t W = LH;
-    size_t lds = collect_lds_bytes(LT, W, L_met, L_vcnt, L_ocnt, 1, pi);
+    size_t lds = collect_lds_bytes(LK, W, L_met, L_vcnt, L_ocnt, 1, pi);
     P.lds_mode = 1;
     P.windowed = 0;
-    if (lds > kLdsPair) {
+    P.cstride = 0;
+    if (rk && L_HIST && LH > 1) {
+        // K x W cells: the window is not grown to what fits (its init and flush scale with K x W) -- ranked_window() keys,
+        // or what the segment's blocks typically span (as below), within the three-workgroups-per-CU budget
+        uint32_t w = std::min<uint32_t>(LH, ranked_window());
+        if (hc && pl.interval > 0) w = std::max<uint32_t>(w, (uint32_t)std::min<int64_t>(hc->zspan / pl.interval + 2, (int64_t)LH));
+        while (w > 1 && collect_lds_bytes(LK, w, L_met, L_vcnt, L_ocnt, 1, pi) > kLdsPair) w = (w + 1) / 2;
+        W = w;
+        P.windowed = W < LH ? 1 : 0;
+        lds = collect_lds_bytes(LK, W, L_met, L_vcnt, L_ocnt, 1, pi);
+    } else if (lds > kLdsPair) {
         if (L_HIST && !P.kslot && !P.hord) {  // the key window needs buckets that rise with the value (zone-map ranges)
             uint32_t w = LH;
             while (w > 1 && collect_lds_bytes(LT, w, L_met, L_vcnt, L_ocnt, 1, pi) > kLdsPair) w = (w + 1) / 2;
@@ -3356,12 +3419,12 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
         const int64_t need = std::min<int64_t>(hc->zspan / pl.interval + 2, (int64_t)LH);
         if (need > (int64_t)W) {
             uint32_t w2 = W;
-            while ((int64_t)w2 < need && collect_lds_bytes(LT, w2 + 1, L_met, L_vcnt, L_ocnt, 1, pi) <= kLdsMax) ++w2;
+            while ((int64_t)w2 < need && collect_lds_bytes(LK, w2 + 1, L_met, L_vcnt, L_ocnt, 1, pi) <= kLdsMax) ++w2;
             if (w2 > W) {
                 W = w2;
                 wide = true;
                 if (W >= LH) { W = LH; P.windowed = 0; }
-                lds = collect_lds_bytes(LT, W, L_met, L_vcnt, L_ocnt, 1, pi);
+                lds = collect_lds_bytes(LK, W, L_met, L_vcnt, L_ocnt, 1, pi);
             }
         }
     }
@@ -3375,6 +3438,18 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
             const size_t b = collect_lds_bytes(LT, W, L_met, L_vcnt, L_ocnt, nc, pi);
             if (b <= kLdsPair) { P.ncopies = nc; lds = b; break; }
         }
+    } else if (rk && P.lds_mode) {
+        // K x W cells leave room for lane-rotated copies of the count + sum words whatever the leaf: the Zipf-head terms of
+        // a wave otherwise queue on one LDS address.  The copies lie cstride cells apart, 33 mod 64 (CollectParams.cstride)
+        // with copies, stats leaves over the 16-bit columns and block-delta keys go without the hot ordinal's register run
+        // (ranked winner cells, VK bit 65536)
+        rkc = L_met == 2 && P.ord16 && P.mv16 && t16 && !wide && b24_fits();
+        const uint32_t cs = ((LK * W + 31u) / 64u) * 64u + 33u;
+        for (uint32_t nc = ranked_copies(); nc > 1; nc /= 2) {
+            const size_t b = collect_lds_bytes(LK, W, L_met, L_vcnt, L_ocnt, nc, pi, cs);
+            if (b <= kLdsPair) { P.ncopies = nc; P.cstride = cs; lds = b; break; }
+        }
+        if (P.ncopies == 1) rkc = false;
     } else if (pi && P.lds_mode && L_HIST && pi_copies(L_met) > 1 && !wide) {
         // packed cells are 16 B instead of 28: a time-sorted window of 2 keys leaves room for lane-rotated copies of the
         // count + sum words (the Zipf-head terms of a wave otherwise queue on one LDS address)
@@ -3429,8 +3504,7 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
         // star 1.28 -> 1.05 ms at 1B, r6ab); with wider displacement every block is multi-key, the kernel is bound by its
         // per-doc work rather than by the bytes, and the 32-bit deltas' simpler unpack measured faster (±1 h: 2.12
         // against 2.27 ms)
-        const bool b24_fits = !t16->b16_hi.p || b24_mode() == 2 || (pl.interval > 0 && !P.kstart && hc->zspan < pl.interval);
-        if (((pi && P.ord16 && P.mv16) || (P.raw_dense && hk_launch == 1)) && b24_fits) {
+        if (((pi && P.ord16 && P.mv16) || (P.raw_dense && hk_launch == 1)) && b24_fits()) {
             P.hv16 = t16->b16.as<uint16_t>();
             P.hv16_base = t16->b16_base.as<int64_t>();
             const bool b24 = t16->b16_hi.p != nullptr;
@@ -3452,10 +3526,11 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
     // than it saves (north star at +-1 h: 2.06 -> 2.40 ms, r6c)
     P.ukey32 = L_HIST && !P.hv16 && P.hv32 && ((pi && P.ord16 && P.mv16) || P.raw_dense) && !P.kstart && hc &&
                pl.interval > 0 && hc->zspan < pl.interval ? 1 : 0;
+    P.rank_cells = rk && rkc && P.hv16 && !fold ? 1 : 0;
     const int vk = (P.hv_f64 ? 1 : 0) | (P.mv_f64 ? 2 : 0) | (P.ord_src ? 8 : 0) | (P.ord16 ? 16 : 0) | (P.hv32 ? 32 : 0) |
                    (pi ? 64 : 0) | (m32 ? 128 : 0) | (P.mv16 ? 256 : 0) | (fold ? 512 : 0) | (P.raw_dense ? 1024 : 0) |
                    (P.runs1 ? 4096 : 0) | (P.hv16 ? 8192 : 0) | (P.ukey32 ? 16384 : 0) |
-                   (P.ocnt_mode != OCNT_TERMS && P.ocnt_mode != OCNT_HIST ? 32768 : 0);
+                   (P.ocnt_mode != OCNT_TERMS && P.ocnt_mode != OCNT_HIST ? 32768 : 0) | (P.rank_cells ? 65536 : 0);
     const uint64_t occ_key = ((uint64_t)lds << 24) | ((uint64_t)wide << 23) | ((uint64_t)vk << 8) | ((uint64_t)L_met << 4) |
                              ((uint64_t)hk << 1) | (L_ORD ? 1 : 0);
     if (pl.occ_key != occ_key) {
@@ -3498,7 +3573,17 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
         P.mv16 = nullptr;
         P.pk_shift = 0;
         P.ncopies = 1;
+        P.cstride = 0;
         goto relaunch;
+    }
+    if (rk) {  // (the rank column is as wide as the 16-bit ordinals it stands in for: the reported bytes do not change)
+        P.T = LK;
+        P.T_full = pl.T;
+        P.rank_ord = rk->ord_of_rank.as<uint32_t>();
+        P.ord16 = rk->rank16.as<uint16_t>();
+        P.ocnt_mode = OCNT_NONE;  // the outer counts are the cached term counts (copied below)
+        for (uint32_t& h : P.hot_t) h = kMissingOrd;
+        P.hot_t[0] = 0;  // the most frequent term has rank 0
     }
     if (pi || m32) bytes_per_doc -= P.mv16 ? 6 : 4;
     if (P.hv16) bytes_per_doc -= P.hv8_and ? 5 : 6;  // (+ one 8-byte base per run, below)
@@ -3543,13 +3628,15 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
         P.npred = 0;
     }
     zero_counts(p, pl);
+    if (rk) HIPX(hipMemcpyAsync(pl.g_ocnt.p, rk->counts.p, (size_t)pl.T * 8, hipMemcpyDeviceToDevice, p->stream));
     launch_collect(P, L_ORD, L_HIST, L_met, wide, grid, lds, p->stream);
     HIPX(hipGetLastError());
     HIPX(hipEventRecord(pl.e1, p->stream));
     dd_fold();
     p->last_bytes += bytes_per_doc * (uint64_t)s->max_doc + (d_accept ? ((uint64_t)s->max_doc + 7) / 8 : 0) +
                      (P.hv16 ? (((uint64_t)s->max_doc + kB16Docs - 1) >> kB16Shift) * 8 : 0);
-    p->last_path = P.lds_mode ? (P.windowed ? 2 : 1) : 0;
+    p->last_path = rk ? 10 : P.lds_mode ? (P.windowed ? 2 : 1) : 0;
+    pl.ranked_live = rk != nullptr;
     return ret;
 }
 
@@ -3616,6 +3703,16 @@ static bool dyn_claim_on() {
 #define ESGPU_PI_COPIES 0
 #endif
 static bool pi_cells(const esgpu_ctx* c) { return c->opt_pi.load() != 0; }
+// ranked terms: the window's keys (ESGPU_RANKED_W, for A/B runs) and the copies of the count + sum words
+// (ESGPU_RANKED_COPIES, 1 = none)
+static uint32_t ranked_window() {
+    static const int v = [] { const char* e = std::getenv("ESGPU_RANKED_W"); return e && *e ? std::atoi(e) : 8; }();
+    return (uint32_t)std::max(v, 1);
+}
+static uint32_t ranked_copies() {
+    static const int v = [] { const char* e = std::getenv("ESGPU_RANKED_COPIES"); return e && *e ? std::atoi(e) : 32; }();
+    return (uint32_t)std::min(std::max(v, 1), 32);
+}
 static uint32_t pi_copies(int met) {
     static const int v = [] {
         const char* e = std::getenv("ESGPU_PI_COPIES");
@@ -3647,6 +3744,53 @@ static const uint16_t* ensure_ord16(esgpu_ctx* c, const DevColumn* col, const es
     HIPX(hipStreamSynchronize(st));
     return m->ord16.as<uint16_t>();
 }
+// ranked terms (ESGPU_OPT_RANKED_TERMS): the column's term counts, frequency ranks and 16-bit rank column, built on the
+// first request that can use them and kept with the column (charged to the HBM budget like the compact copies; over the
+// budget: null, and the request collects every term).  ord16: the column's 16-bit ordinals (ensure_ord16).
+static bool ranked_terms_on(const esgpu_ctx* c) { return c->opt_ranked.load() != 0; }
+static const TermRanks* ensure_term_ranks(esgpu_ctx* c, const DevColumn* col, const uint16_t* ord16, const esgpu_segment* s,
+                                          hipStream_t st) {
+    DevColumn* m = const_cast<DevColumn*>(col);
+    const uint32_t T = (uint32_t)col->value_count;
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        if (m->ranks_done) return m->ranks.get();
+        m->ranks_done = true;
+    }
+    // (built outside the lock: count_all_ordinals synchronises; a plan on another thread that asks meanwhile collects
+    // every term this once)
+    std::unique_ptr<TermRanks> r(new TermRanks());
+    try {
+        r->T = T;
+        DevBuf c32;
+        count_all_ordinals(c, col->values.as<uint32_t>(), s->max_doc, s->n_pad, T, c32, st);
+        std::vector<uint32_t> h32(T);
+        HIPX(hipMemcpyAsync(h32.data(), c32.p, (size_t)T * 4, hipMemcpyDeviceToHost, st));
+        HIPX(hipStreamSynchronize(st));
+        std::vector<uint64_t> counts(h32.begin(), h32.end());
+        std::vector<uint32_t> rank_of(T), ord_of_rank(T);
+        rank_terms_by_count(counts.data(), T, rank_of.data(), ord_of_rank.data());
+        std::vector<uint16_t> rank16(rank_of.begin(), rank_of.end());  // (T < 0xFFFF)
+        DevBuf d_rank_of;
+        d_rank_of.alloc(c, (size_t)T * 2);
+        r->counts.alloc(c, (size_t)T * 8);
+        r->ord_of_rank.alloc(c, (size_t)T * 4);
+        r->rank16.alloc(c, (size_t)s->n_pad * 2);
+        HIPX(hipMemcpyAsync(d_rank_of.p, rank16.data(), (size_t)T * 2, hipMemcpyHostToDevice, st));
+        HIPX(hipMemcpyAsync(r->counts.p, counts.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
+        HIPX(hipMemcpyAsync(r->ord_of_rank.p, ord_of_rank.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
+        launch_rank_ord16(ord16, s->n_pad, d_rank_of.as<uint16_t>(), T, r->rank16.as<uint16_t>(), st);
+        HIPX(hipGetLastError());
+        HIPX(hipStreamSynchronize(st));  // (the host vectors and d_rank_of go out of scope)
+    } catch (const EsError& e) {
+        if (e.code != ESGPU_ERR_OOM) throw;
+        return nullptr;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    m->ranks = std::move(r);
+    return m->ranks.get();
+}
+
 // the 4 most frequent ordinals among 64 evenly spaced runs of 4,096 docs, most frequent first (cached with the ordinal
 // buffer; kMissingOrd where fewer ordinals occur)
 static void sampled_hot_ords(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, uint32_t (&out)[4]) {
@@ -4132,14 +4276,31 @@ extern "C" int esgpu_plan_collect_segment(esgpu_plan* p, const esgpu_segment* s,
             HIPX(hipStreamSynchronize(p->stream));
             d_accept = (const uint64_t*)a;
         }
+        // ranked terms: a second segment reaches a plan whose first was collected over its top-ranked terms alone -- the
+        // shard's winners are no longer that segment's, so its partial grid is dropped, the retained segment collected
+        // again over every term, and the plan stays off the ranked path (it serves this shard: the waste happens once)
+        for (Pipeline& pl : p->pipes) {
+            if (!pl.ranked_live) continue;
+            require(!p->dsegs.empty(), ESGPU_ERR_STATE, "internal: ranked collect without its retained segment");
+            clear_grid(p, pl);
+            pl.ranked_live = false;
+            pl.ranked_off = true;
+            pl.fresh = true;
+            collect_grid(p, pl, p->dsegs[0].s, nullptr);
+        }
         p->last_bytes = 0;
         p->last_ms = -1;
         p->zu_n = 0;
-        bool deferred = false;
+        bool deferred = false, ranked = false;
         for (Pipeline& pl : p->pipes) {
             if (pl.replay) { pl.timed = false; continue; }
             pl.timed = pl.kind == 1 ? collect_hll(p, pl, s, d_accept) : collect_grid(p, pl, s, d_accept);
             deferred |= pl.timed && pl.deferred;
+            ranked |= pl.kind != 1 && pl.ranked_live;
+        }
+        if (ranked && p->dsegs.empty()) {  // retained until the plan's reset (no accept bits: the ranked path takes none)
+            pin_segment(s);
+            p->dsegs.push_back(esgpu_plan::DeferredSeg{s, -1});
         }
         if (deferred) {  // BestBucketsDeferringCollector: the segment (and its accept bits) kept for the replay at build
             esgpu_plan::DeferredSeg d{s, -1};
@@ -6004,6 +6165,47 @@ extern "C" int esgpu_plan_build(esgpu_plan* p, esgpu_result** out) {
     });
 }
 
+// a cell-grid pipeline's accumulators back to their initial values (reset; the ranked-terms fallback)
+static void clear_grid(esgpu_plan* p, Pipeline& pl) {
+    const size_t cells = (size_t)pl.T * pl.H;
+    for (CardState& cs : pl.cards) {
+        HIPX(hipMemsetAsync(cs.regs.p, 0, cs.regs.bytes, p->stream));
+        HIPX(hipMemsetAsync(cs.sets.p, 0, cs.sets.bytes, p->stream));
+        HIPX(hipMemsetAsync(cs.first.p, 0xFF, cs.first.bytes, p->stream));
+        HIPX(hipMemsetAsync(cs.cnt.p, 0, cs.cnt.bytes, p->stream));
+        HIPX(hipMemsetAsync(cs.nonzero.p, 0, cs.nonzero.bytes, p->stream));
+    }
+    // the grid's arrays in one launch (one per pipeline instead of one per array: a multi-shard request resets
+    // every shard's plan, and each launch costs host time)
+    FillList fl{};
+    auto span = [&](void* ptr, size_t n, unsigned long long v) {
+        if (!ptr || n == 0) return;
+        fl.p[fl.count] = (unsigned long long*)ptr;
+        fl.n[fl.count] = n;
+        fl.v[fl.count] = v;
+        if (++fl.count == kFillSpans) { launch_fill_multi(fl, p->stream); fl.count = 0; }
+    };
+    // the counts: with the other arrays in this launch where the grid is small (the north star's 5.8 MB: one
+    // launch fewer ahead of the next collect), else at the request's first collect or build (zero_counts: a
+    // high-cardinality terms grid's first hot/cold segment writes its counts itself)
+    pl.zero_pending = pl.g_cnt.p != nullptr;
+    if (pl.zero_pending && eager_zero_on() && !pl.cnt32 && (size_t)pl.T * pl.H * 8 <= (16u << 20)) {
+        span(pl.g_cnt.p, (size_t)pl.T * pl.H, 0ull);
+        pl.zero_pending = false;
+    }
+    if (pl.g_ocnt.p) {
+        if (pl.g_ocnt.bytes % 8 == 0) span(pl.g_ocnt.p, pl.g_ocnt.bytes / 8, 0ull);
+        else HIPX(hipMemsetAsync(pl.g_ocnt.p, 0, pl.g_ocnt.bytes, p->stream));
+    }
+    span(pl.g_vcnt.p, cells, 0ull);
+    span(pl.g_sum.p, cells, 0ull);
+    span(pl.g_min.p, cells, kMinInit);
+    span(pl.g_max.p, cells, kMaxInit);
+    span(pl.g_sq.p, cells, 0ull);
+    if (fl.count) launch_fill_multi(fl, p->stream);
+    HIPX(hipGetLastError());
+}
+
 extern "C" int esgpu_plan_reset(esgpu_plan* p) {
     return guarded([&] {
         require(p != nullptr, ESGPU_ERR_INVALID, "null plan");
@@ -6037,48 +6239,13 @@ extern "C" int esgpu_plan_reset(esgpu_plan* p) {
                 pl.hll_nseg = 0;
                 continue;
             }
-            const size_t cells = (size_t)pl.T * pl.H;
-            for (CardState& cs : pl.cards) {
-                HIPX(hipMemsetAsync(cs.regs.p, 0, cs.regs.bytes, p->stream));
-                HIPX(hipMemsetAsync(cs.sets.p, 0, cs.sets.bytes, p->stream));
-                HIPX(hipMemsetAsync(cs.first.p, 0xFF, cs.first.bytes, p->stream));
-                HIPX(hipMemsetAsync(cs.cnt.p, 0, cs.cnt.bytes, p->stream));
-                HIPX(hipMemsetAsync(cs.nonzero.p, 0, cs.nonzero.bytes, p->stream));
-            }
-            // the grid's arrays in one launch (one per pipeline instead of one per array: a multi-shard request resets
-            // every shard's plan, and each launch costs host time)
-            FillList fl{};
-            auto span = [&](void* ptr, size_t n, unsigned long long v) {
-                if (!ptr || n == 0) return;
-                fl.p[fl.count] = (unsigned long long*)ptr;
-                fl.n[fl.count] = n;
-                fl.v[fl.count] = v;
-                if (++fl.count == kFillSpans) { launch_fill_multi(fl, p->stream); fl.count = 0; }
-            };
-            // the counts: with the other arrays in this launch where the grid is small (the north star's 5.8 MB: one
-            // launch fewer ahead of the next collect), else at the request's first collect or build (zero_counts: a
-            // high-cardinality terms grid's first hot/cold segment writes its counts itself)
-            pl.zero_pending = pl.g_cnt.p != nullptr;
-            if (pl.zero_pending && eager_zero_on() && !pl.cnt32 && (size_t)pl.T * pl.H * 8 <= (16u << 20)) {
-                span(pl.g_cnt.p, (size_t)pl.T * pl.H, 0ull);
-                pl.zero_pending = false;
-            }
-            if (pl.g_ocnt.p) {
-                if (pl.g_ocnt.bytes % 8 == 0) span(pl.g_ocnt.p, pl.g_ocnt.bytes / 8, 0ull);
-                else HIPX(hipMemsetAsync(pl.g_ocnt.p, 0, pl.g_ocnt.bytes, p->stream));
-            }
-            span(pl.g_vcnt.p, cells, 0ull);
-            span(pl.g_sum.p, cells, 0ull);
-            span(pl.g_min.p, cells, kMinInit);
-            span(pl.g_max.p, cells, kMaxInit);
-            span(pl.g_sq.p, cells, 0ull);
-            if (fl.count) launch_fill_multi(fl, p->stream);
-            HIPX(hipGetLastError());
+            clear_grid(p, pl);
         }
         p->posted = false;
         p->collected = false;
         p->seg_seq = 0;
         p->docs_seen = 0;
+        for (Pipeline& pl : p->pipes) pl.ranked_live = false;
         p->unpin_all();
     });
 }

@@ -280,10 +280,11 @@ class Engine:
         return v.value
 
     OPTIONS = {"compact_columns": 1, "packed_metric": 2, "hll_floor": 3, "block_deltas": 4,
-               "numeric_terms_max_distinct": 5}  # include/esgpu.h ESGPU_OPT_*
+               "numeric_terms_max_distinct": 5, "ranked_terms": 6}  # include/esgpu.h ESGPU_OPT_*
 
     def set_option(self, name, value):
-        """Layout option of this context (esgpu_ctx_set_option): 'compact_columns' / 'packed_metric' / 'block_deltas', 0 or 1;
+        """Layout option of this context (esgpu_ctx_set_option): 'compact_columns' / 'packed_metric' / 'block_deltas' /
+        'ranked_terms', 0 or 1;
         'hll_floor' 0..8 (include/esgpu.h ESGPU_OPT_HLL_FLOOR); 'numeric_terms_max_distinct': the distinct values of a long field
         in one segment above which terms over it are refused (default 2^22)."""
         N.check(N.lib().esgpu_ctx_set_option(self._ptr, self.OPTIONS[name], int(value)))

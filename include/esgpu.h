@@ -83,13 +83,18 @@ int esgpu_device_count(int* count);
  *   ESGPU_OPT_BLOCK_DELTAS:    a dense time-sorted key column whose every run of 2,048 docs spans < 2^16 is read by
  *                              the raw-load collect kernels as 16-bit deltas over each run's minimum (2 B per doc
  *                              instead of 4; needs compact columns; ESGPU_B16=0 turns the default off)
+ *   ESGPU_OPT_RANKED_TERMS:    an unfiltered top-level terms aggregation in count order over a shard's only segment
+ *                              collects its sub-aggregations for the top shard_size terms alone, known beforehand from
+ *                              the segment's term counts (the reference's breadth_first collect mode with the counting
+ *                              pass cached per segment).  0 collects every term.  Not read from the
+ *                              environment.
  * and one limit:
  *   ESGPU_OPT_NUMERIC_TERMS_MAX_DISTINCT: terms over a long / date field count by the segment's numeric ordinals; a
  *                              segment with more distinct values than this (default 2^22) is refused with
  *                              ESGPU_ERR_UNSUPPORTED (its hash set holds twice as many slots) */
 enum {
     ESGPU_OPT_COMPACT_COLUMNS = 1, ESGPU_OPT_PACKED_METRIC = 2, ESGPU_OPT_HLL_FLOOR = 3, ESGPU_OPT_BLOCK_DELTAS = 4,
-    ESGPU_OPT_NUMERIC_TERMS_MAX_DISTINCT = 5
+    ESGPU_OPT_NUMERIC_TERMS_MAX_DISTINCT = 5, ESGPU_OPT_RANKED_TERMS = 6
 };
 int esgpu_ctx_set_option(esgpu_ctx* ctx, int32_t option, int64_t value);
 int esgpu_ctx_get_option(const esgpu_ctx* ctx, int32_t option, int64_t* value);
@@ -389,7 +394,8 @@ int esgpu_plan_destroy(esgpu_plan* plan);
  * and the algorithmic bytes it read (SURVEY §8(d) formula).  path: the collect form -- 0 grid in global memory,
  * 1 LDS grid, 2 LDS key window, 3 HLL registers, 4 partitioned terms counting, 5 multi-valued (CSR) columns, 6 hot/cold
  * terms scatter form, 7 hot/cold postings form, 8 hot slots only (cold lists deferred to the top-k), 9 hot slots of a
- * filtered request (the scatter form deferred to the top-k). */
+ * filtered request (the scatter form deferred to the top-k), 10 LDS key window over the top-ranked terms (the segment
+ * is retained -- esgpu_plan_deferred_segments -- and collected again over every term if the request brings a second). */
 int esgpu_plan_last_collect_stats(const esgpu_plan* plan, double* kernel_ms, uint64_t* algorithmic_bytes,
                                   int32_t* path);
 /* Wall time of the last esgpu_plan_build and the part of it spent waiting on the plan's stream (gathers and copies of
@@ -403,7 +409,7 @@ int esgpu_plan_shard_mergeable(const esgpu_plan* plan, int32_t* mergeable);
 /* Segments the plan retains for a breadth-first replay at build (TermsAggregator breadth_first collect mode,
  * BestBucketsDeferringCollector.java:96-166): a terms-under-terms child whose [outer x inner] grid is over the dense
  * budget counts only the outer buckets while collecting and is collected again at build over the retained segments for
- * the surviving outer buckets.  A retained segment stays valid until the plan's reset / destroy even if
+ * the surviving outer buckets.  A ranked-terms collect (path 10) retains its one segment too.  A retained segment stays valid until the plan's reset / destroy even if
  * esgpu_segment_destroy is called on it first (its destroy is then carried out at that point). */
 int esgpu_plan_deferred_segments(const esgpu_plan* plan, int32_t* segments);
 
