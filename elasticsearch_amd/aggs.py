@@ -286,6 +286,26 @@ class AvgBuilder(_MetricBuilder):
     type = N.AGG_AVG
 
 
+class SumBuilder(_MetricBuilder):
+    """sum (SumAggregator / InternalSum): {"value": the sum of the field's values, 0.0 when there are none}"""
+    type = N.AGG_SUM
+
+
+class MinBuilder(_MetricBuilder):
+    """min (MinAggregator / InternalMin): +Infinity when no doc has a value (XContent: null)"""
+    type = N.AGG_MIN
+
+
+class MaxBuilder(_MetricBuilder):
+    """max (MaxAggregator / InternalMax): -Infinity when no doc has a value (XContent: null)"""
+    type = N.AGG_MAX
+
+
+class ValueCountBuilder(_MetricBuilder):
+    """value_count (ValueCountAggregator / InternalValueCount): the number of values, over numeric and keyword fields"""
+    type = N.AGG_VALUE_COUNT
+
+
 class CardinalityBuilder(_MetricBuilder):
     type = N.AGG_CARDINALITY
 
@@ -331,6 +351,10 @@ class AggregationBuilders:
     extendedStats = ExtendedStatsBuilder
     extended_stats = ExtendedStatsBuilder
     avg = AvgBuilder
+    sum = SumBuilder
+    min = MinBuilder
+    max = MaxBuilder
+    count = ValueCountBuilder  # AggregationBuilders.count(name) builds the value_count aggregation
     cardinality = CardinalityBuilder
 
 

@@ -449,6 +449,16 @@ void launch_numord_hash_rank(const unsigned long long* table, uint32_t slots, co
 void launch_numord_encode_hash(const int64_t* v, const uint64_t* present, uint32_t n_docs, uint32_t n_pad,
                                const unsigned long long* table, uint32_t slots, uint32_t probe_limit, const uint32_t* slot_rank,
                                uint32_t sentinel_rank, uint32_t* ord, hipStream_t st);
+// ---- the per-doc value-count product (esgpu_valcount.hip): one u16 per doc of [0, n_pad), 0 past n_docs ----
+// ord: a single-valued ordinal column, `width` 4 (missing 0xFFFFFFFF) or 2 (its 16-bit copy, missing 0xFFFF); present: a
+// bitset of at least n_docs bits; offsets: CSR offsets [n_docs + 1], with *vmax raised to the largest per-doc count
+// (counts are stored modulo 2^16: a caller that reads *vmax > 65,535 drops the product); ones: every doc holds one value
+void launch_value_counts_ord(const void* ord, int width, uint32_t n_docs, uint32_t n_pad, uint16_t* out, hipStream_t st);
+void launch_value_counts_present(const uint64_t* present, uint32_t n_docs, uint32_t n_pad, uint16_t* out, hipStream_t st);
+void launch_value_counts_csr(const uint64_t* offsets, uint32_t n_docs, uint32_t n_pad, uint16_t* out, unsigned int* vmax, hipStream_t st);
+void launch_value_counts_ones(uint32_t n_docs, uint32_t n_pad, uint16_t* out, hipStream_t st);
+// out[i] = (double)cnt[i]
+void launch_counts_to_f64(const unsigned long long* cnt, size_t n, double* out, hipStream_t st);
 void launch_delta16(const int64_t* v, uint32_t n, int64_t base, uint16_t* out, hipStream_t st);
 void launch_delta32(const int64_t* v, uint32_t n, int64_t base, uint32_t* out, hipStream_t st);
 // breadth-first replay, compacted: one pass over a retained segment appends, for every doc whose outer bucket survived

@@ -99,6 +99,14 @@ bool metric_value(int type, const std::string& key, int64_t count, double sum, d
         *out = avg;
         return true;
     }
+    if (is_single_value_metric(type)) {
+        // SumAggregator.metric (A/metrics/sum/SumAggregator.java:92-95), MinAggregator.metric (A/metrics/min/
+        // MinAggregator.java:99-102), MaxAggregator.metric (A/metrics/max/MaxAggregator.java:100-103), ValueCountAggregator
+        // .metric (A/metrics/valuecount/ValueCountAggregator.java:89-92): an empty bucket's 0 / +Inf / -Inf / 0, never NaN
+        if (!key.empty() && key != "value") return false;
+        *out = type == ESGPU_AGG_SUM ? sum : type == ESGPU_AGG_MIN ? min : type == ESGPU_AGG_MAX ? max : (double)count;
+        return true;
+    }
     if (key == "count") *out = (double)count;
     else if (key == "sum") *out = sum;
     else if (key == "min") *out = min;
@@ -423,11 +431,15 @@ struct Scratch {
 // numeric metric sub-aggregations of a bucket reduce are reduced as their bucket is emitted (no child level): their
 // reduce reads nothing but the contributions' partials, and instances are appended in emission order either way
 inline bool fused_leaf(const Block& b) {
-    return b.type == ESGPU_AGG_STATS || b.type == ESGPU_AGG_EXTENDED_STATS || b.type == ESGPU_AGG_AVG;
+    return b.type == ESGPU_AGG_STATS || b.type == ESGPU_AGG_EXTENDED_STATS || b.type == ESGPU_AGG_AVG ||
+           is_single_value_metric(b.type);
 }
 
 // InternalStats / InternalExtendedStats / InternalAvg .doReduce of sub-aggregation j over contributions [c0, c1) (shard
-// order): sums in that order from 0, Math.min / Math.max
+// order): sums in that order from 0, Math.min / Math.max.  InternalSum / InternalMin / InternalMax / InternalValueCount
+// .doReduce (InternalSum.java:82-88, InternalMin.java:82-88, InternalMax.java:81-87, InternalValueCount.java:82-88) are
+// the same operators on the one array each of them fills; their other arrays hold the empty instance's values, which
+// every operator leaves alone
 void reduce_leaf(Block& m, const Scratch& sc, size_t j, uint32_t c0, uint32_t c1) {
     int64_t count = 0;
     double mn = INFINITY, mx = -INFINITY, sum = 0, sq = 0;
@@ -1158,6 +1170,39 @@ std::string long_key_string(const Block& a, uint64_t k) {
     return std::to_string((long long)a.long_key(k));
 }
 
+// ---- sum / min / max / value_count: the one value of instance i and its formatted form ----
+// InternalSum.value / InternalMin.value / InternalMax.value (a double); InternalValueCount.value is a long (count)
+double single_value(const Block& a, uint64_t i) {
+    switch (a.type) {
+        case ESGPU_AGG_SUM: return a.sum[i];
+        case ESGPU_AGG_MIN: return a.min[i];
+        case ESGPU_AGG_MAX: return a.max[i];
+        default: return (double)a.count[i];
+    }
+}
+// doXContentBody prints value_as_string when the formatter is not RAW (InternalSum.java:103-109, InternalValueCount
+// .java:103-109) and, for min / max, only when there is a value (InternalMin.java:103-110, InternalMax.java:102-109)
+bool single_value_has_string(const Block& a, uint64_t i) {
+    if (a.value_format == ESGPU_FORMAT_RAW) return false;
+    if (a.type == ESGPU_AGG_MIN) return !std::isinf(a.min[i]);
+    if (a.type == ESGPU_AGG_MAX) return !std::isinf(a.max[i]);
+    return true;
+}
+// ValueFormatter.format: DateTime prints (long) value with the field's printer in UTC (ValueFormatter.java:139-147: a
+// metric has no time zone); a number pattern is not rendered (no DecimalFormat here, as for LongTerms keys) and prints
+// the value as Java prints it
+std::string single_value_string(const Block& a, uint64_t i) {
+    if (a.type == ESGPU_AGG_VALUE_COUNT)
+        return a.value_format == ESGPU_FORMAT_DATE_TIME ? es_date(a.count[i], {}, {}) : std::to_string((long long)a.count[i]);
+    const double v = single_value(a, i);
+    if (a.value_format == ESGPU_FORMAT_DATE_TIME) {
+        // Java's (long) cast: NaN -> 0, saturating at the ends
+        const int64_t ms = v != v ? 0 : v >= 9223372036854775807.0 ? INT64_MAX : v <= -9223372036854775808.0 ? INT64_MIN : (int64_t)v;
+        return es_date(ms, {}, {});
+    }
+    return java_double(v);
+}
+
 void write_instance(J& j, const Block& a, uint64_t i);
 
 void write_subs(J& j, const Block& a, uint64_t k) {
@@ -1214,6 +1259,18 @@ void write_instance(J& j, const Block& a, uint64_t i) {
             j.key("value"); j.opt(a.count[i] != 0, a.sum[i] / (double)a.count[i]);
             j.raw(","); j.key("_internal"); j.raw("{"); j.key("count"); j.i64(a.count[i]); j.raw(",");
             j.key("sum"); j.dbl(a.sum[i]); j.raw("}");
+            break;
+        case ESGPU_AGG_SUM:
+        case ESGPU_AGG_MIN:
+        case ESGPU_AGG_MAX: {  // the value itself (an empty min / max: +-Infinity, which XContent prints as null)
+            const double v = single_value(a, i);
+            j.key("value"); j.dbl(v);
+            if (single_value_has_string(a, i)) { j.raw(","); j.key("value_as_string"); j.str(single_value_string(a, i)); }
+            break;
+        }
+        case ESGPU_AGG_VALUE_COUNT:
+            j.key("value"); j.i64(a.count[i]);
+            if (single_value_has_string(a, i)) { j.raw(","); j.key("value_as_string"); j.str(single_value_string(a, i)); }
             break;
         case ESGPU_AGG_STATS:
         case ESGPU_AGG_EXTENDED_STATS: {
@@ -1410,6 +1467,19 @@ void x_instance(X& x, const Block& a, uint64_t i) {
         case ESGPU_AGG_AVG:
             x.key("value"); x.opt(a.count[i] != 0, a.sum[i] / (double)a.count[i]);
             break;
+        case ESGPU_AGG_SUM:  // InternalSum.doXContentBody (InternalSum.java:103-109)
+            x.key("value"); x.dbl(a.sum[i]);
+            if (single_value_has_string(a, i)) { x.raw(","); x.key("value_as_string"); x.str(single_value_string(a, i)); }
+            break;
+        case ESGPU_AGG_MIN:  // InternalMin.doXContentBody (InternalMin.java:103-110): null unless a value was collected
+        case ESGPU_AGG_MAX:  // InternalMax.doXContentBody (InternalMax.java:102-109)
+            x.key("value"); x.opt(!std::isinf(single_value(a, i)), single_value(a, i));
+            if (single_value_has_string(a, i)) { x.raw(","); x.key("value_as_string"); x.str(single_value_string(a, i)); }
+            break;
+        case ESGPU_AGG_VALUE_COUNT:  // InternalValueCount.doXContentBody (InternalValueCount.java:103-109): a long
+            x.key("value"); x.i64(a.count[i]);
+            if (single_value_has_string(a, i)) { x.raw(","); x.key("value_as_string"); x.str(single_value_string(a, i)); }
+            break;
         case ESGPU_AGG_STATS:
         case ESGPU_AGG_EXTENDED_STATS: {
             const int64_t cnt = a.count[i];
@@ -1518,6 +1588,10 @@ const char* stream_type(int32_t type) {  // InternalAggregation.Type stream name
         case ESGPU_AGG_STATS: return "stats";                // InternalStats.java:41
         case ESGPU_AGG_EXTENDED_STATS: return "estats";      // InternalExtendedStats.java:41
         case ESGPU_AGG_AVG: return "avg";                    // InternalAvg.java:40
+        case ESGPU_AGG_SUM: return "sum";                    // InternalSum.java:40
+        case ESGPU_AGG_MIN: return "min";                    // InternalMin.java:40
+        case ESGPU_AGG_MAX: return "max";                    // InternalMax.java:40
+        case ESGPU_AGG_VALUE_COUNT: return "value_count";    // InternalValueCount.java:40
         case ESGPU_AGG_CARDINALITY: return "cardinality";    // InternalCardinality.java:39
         case ESGPU_AGG_FILTER: return "filter";              // InternalFilter.java:36
     }
@@ -1658,6 +1732,16 @@ void es_instance(JavaOut& w, const Block& a, uint64_t i) {
         case ESGPU_AGG_AVG:  // InternalAvg.doWriteTo (:102-106)
             write_formatter(w, a);
             w.f64(a.sum[i]);
+            w.vlong(a.count[i]);
+            break;
+        case ESGPU_AGG_SUM:  // InternalSum.doWriteTo (InternalSum.java:97-100)
+        case ESGPU_AGG_MIN:  // InternalMin.doWriteTo (InternalMin.java:97-100)
+        case ESGPU_AGG_MAX:  // InternalMax.doWriteTo (InternalMax.java:96-99)
+            write_formatter(w, a);
+            w.f64(single_value(a, i));
+            break;
+        case ESGPU_AGG_VALUE_COUNT:  // InternalValueCount.doWriteTo (InternalValueCount.java:97-100)
+            write_formatter(w, a);
             w.vlong(a.count[i]);
             break;
         case ESGPU_AGG_CARDINALITY:  // InternalCardinality.doWriteTo (:92-100), HyperLogLogPlusPlus.writeTo (:519-535)
@@ -1830,6 +1914,11 @@ void r_block(R& r, Block& a, int depth) {
     } else if (a.count.size() != a.n || a.sum.size() != a.n || a.min.size() != a.n || a.max.size() != a.n ||
                a.sumsq.size() != a.n) {
         throw std::runtime_error("inconsistent metric block");
+    } else if (is_single_value_metric(a.type) &&
+               (!a.boff.empty() || !a.key.empty() || !a.bcount.empty() || !a.berr.empty() || !a.term_off.empty() ||
+                !a.term_pool.empty() || !a.doc_count_error.empty() || !a.other_doc_count.empty() || !a.subs.empty() ||
+                !a.empty_subs.empty() || !a.hll_present.empty() || !a.regs.empty() || !a.lc.empty())) {
+        throw std::runtime_error("bucket payload on a single-value metric block");
     }
 }
 void r_blocks(R& r, std::vector<Block>& l, int depth) {
@@ -1954,7 +2043,26 @@ const esgpu_agg_block* export_blocks(ResultHolder& h, const std::vector<Block>& 
 }
 }  // namespace
 
+namespace {
+// A sum / min / max / value_count block keeps the one partial its InternalAggregation holds; the arrays it shares with
+// the stats blocks but does not fill hold the empty instance's values (count 0, sum 0.0, min +Inf, max -Inf), whatever
+// the grid's cells collected beside it -- so the C view, the shard record and every reduce see only that partial
+void keep_single_values(std::vector<Block>& l) {
+    for (Block& a : l) {
+        keep_single_values(a.subs);
+        keep_single_values(a.empty_subs);
+        if (!is_single_value_metric(a.type)) continue;
+        if (a.type != ESGPU_AGG_VALUE_COUNT) std::fill(a.count.begin(), a.count.end(), 0);
+        if (a.type != ESGPU_AGG_SUM) std::fill(a.sum.begin(), a.sum.end(), 0.0);
+        if (a.type != ESGPU_AGG_MIN) std::fill(a.min.begin(), a.min.end(), (double)INFINITY);
+        if (a.type != ESGPU_AGG_MAX) std::fill(a.max.begin(), a.max.end(), -(double)INFINITY);
+        std::fill(a.sumsq.begin(), a.sumsq.end(), 0.0);
+    }
+}
+}  // namespace
+
 void ResultHolder::export_view() {
+    keep_single_values(aggs);
     views.clear();
     reg_ptrs.clear();
     lc_ptrs.clear();
@@ -1988,7 +2096,9 @@ inline uint64_t enc_max(double x) { return x != x ? ~0ULL : enc_dbl(x); }
 inline double dec_min(uint64_t e) { return e == 0 ? NAN : dec_dbl(e); }
 inline double dec_max(uint64_t e) { return e == ~0ULL ? NAN : dec_dbl(e); }
 
-bool is_numeric_metric(int t) { return t == ESGPU_AGG_STATS || t == ESGPU_AGG_EXTENDED_STATS || t == ESGPU_AGG_AVG; }
+bool is_numeric_metric(int t) {
+    return t == ESGPU_AGG_STATS || t == ESGPU_AGG_EXTENDED_STATS || t == ESGPU_AGG_AVG || is_single_value_metric(t);
+}
 
 // a top-level aggregation whose shard partials have a fixed shape once the bucket keys are agreed on
 bool fixed_shape(const Block& b) {

@@ -97,11 +97,15 @@ struct Block {
 void merge_long_dicts(const std::vector<const std::vector<int64_t>*>& segs, std::vector<int64_t>& global,
                       std::vector<std::vector<uint32_t>>& maps);
 
+// sum / min / max / value_count: single-value numeric metrics whose block fills one of the stats arrays (sum -> sum,
+// min -> min, max -> max, value_count -> count)
+inline bool is_single_value_metric(int t) { return t >= ESGPU_AGG_SUM && t <= ESGPU_AGG_VALUE_COUNT; }
+
 // ---- terms ordered by a metric sub-aggregation (InternalOrder.Aggregation) ----
 // AggregationPath.parse of a one-element path: "name", "name.key" or "name[key]" (key empty when absent)
 bool parse_order_path(const std::string& path, std::string* name, std::string* key);
 // the metric the path's key names, with Java double arithmetic: InternalAvg.value / InternalStats.value(name) /
-// InternalExtendedStats.value(name), equal to the shard-level AvgAggregator.metric / StatsAggegator.metric /
+// InternalExtendedStats.value(name) / the value of a sum, min, max or value_count, equal to the shard-level AvgAggregator.metric / StatsAggegator.metric /
 // ExtendedStatsAggregator.metric(name, bucket); returns false for a key the metric does not have
 bool metric_value(int type, const std::string& key, int64_t count, double sum, double min, double max, double sumsq,
                   double sigma, double* out);

@@ -372,6 +372,9 @@ struct DevColumn {
     // an ORD_U32 column over the segment's numeric dictionary -- the rank of each doc's value among the distinct values
     // of ALL the segment's docs -- which terms over the field count by like a keyword column (global ordinals included)
     std::unique_ptr<DevColumn> num_view;
+    // the per-doc value-count product of the column (ensure_value_counts, built on first use and cached with the column):
+    // a dense long column that owns only its 16-bit deltas
+    std::unique_ptr<DevColumn> vc_view;
     const DevColumn* num_src = nullptr;  // on the view: the long column it was built from
     // the dictionary on the device (sorted longs): part of the product; after the build no kernel reads it yet (terms are
     // resolved on the host through dict->longs)
@@ -951,7 +954,10 @@ extern "C" int esgpu_precision_from_threshold(int64_t count, int32_t* precision)
 // plans
 // ------------------------------------------------------------------------------------------------------------
 static bool is_bucket(int t) { return t == ESGPU_AGG_TERMS || t == ESGPU_AGG_HISTOGRAM || t == ESGPU_AGG_DATE_HISTOGRAM; }
-static bool is_metric(int t) { return t == ESGPU_AGG_STATS || t == ESGPU_AGG_EXTENDED_STATS || t == ESGPU_AGG_AVG; }
+// numeric metrics collected in a cell grid: stats / extended_stats / avg and the single-value sum / min / max / value_count
+static bool is_metric(int t) {
+    return t == ESGPU_AGG_STATS || t == ESGPU_AGG_EXTENDED_STATS || t == ESGPU_AGG_AVG || is_single_value_metric(t);
+}
 
 struct SpecNode {
     esgpu_agg_spec s;
@@ -1024,6 +1030,12 @@ struct Pipeline {
     DevBuf d_ostart, d_oslot;
     std::shared_ptr<DevColumn> ord_col;
     int met = 0;                     // 0 none, 1 avg, 2 stats, 3 extended
+    bool sums = false;               // some leaf reports the cells' sums (only min / max / value_count leaves: none does)
+    // value_count leaves alone over their field (ValueCountAggregator.java:75-88): nothing reads the field's values.
+    // While every segment's column is dense and single-valued the value count is the doc count (met stays 0, no metric
+    // column); from the first segment that is not (sparse, multi-valued, keyword, or lacking the field) the pipeline
+    // collects the per-doc value-count product as a dense integer metric (vc_prod: met = 1, count = (int64) sum)
+    bool vc_only = false, vc_prod = false;
     int64_t interval = 1, offset = 0;  // affine roundings: key = floor((v - offset) / interval) * interval + offset
     Rounding rnd;                    // the histogram spec's rounding
     bool ktable = false;             // non-affine rounding: bucket start table instead of the affine map
@@ -1226,7 +1238,20 @@ struct esgpu_plan {
     }
 };
 
-static int metric_level(int t) { return t == ESGPU_AGG_AVG ? 1 : t == ESGPU_AGG_STATS ? 2 : 3; }
+// the cells a metric leaf needs: 1 count + sum (avg, sum), 2 + min / max (stats, min, max), 3 + sum of squares; a
+// value_count needs none of its own (the pipeline's value count)
+static int metric_level(int t) {
+    switch (t) {
+        case ESGPU_AGG_VALUE_COUNT: return 0;
+        case ESGPU_AGG_AVG: case ESGPU_AGG_SUM: return 1;
+        case ESGPU_AGG_STATS: case ESGPU_AGG_MIN: case ESGPU_AGG_MAX: return 2;
+        default: return 3;
+    }
+}
+static bool metric_has_sum(int t) { return t == ESGPU_AGG_AVG || t == ESGPU_AGG_SUM || t == ESGPU_AGG_STATS || t == ESGPU_AGG_EXTENDED_STATS; }
+static bool metric_has_extrema(int t) {
+    return t == ESGPU_AGG_STATS || t == ESGPU_AGG_EXTENDED_STATS || t == ESGPU_AGG_MIN || t == ESGPU_AGG_MAX;
+}
 
 static int64_t key_value(const Pipeline& pl, uint32_t slot) {
     return pl.ktable ? pl.kt_key[slot] : (pl.key0 + (int64_t)slot) * pl.interval + pl.offset;
@@ -1295,6 +1320,11 @@ static int add_pipeline(esgpu_plan* p, int root, int fspec, int outer, int inner
         }
         if (pl.metric_field.empty()) pl.metric_field = n.field;
         pl.met = std::max(pl.met, metric_level(n.s.type));
+        pl.sums = pl.sums || metric_has_sum(n.s.type);
+    }
+    if (pl.met == 0 && !pl.metric_field.empty()) {  // value_count leaves only (the product's sums are read)
+        pl.vc_only = true;
+        pl.sums = true;
     }
     p->pipes.push_back(std::move(pl));
     return (int)p->pipes.size() - 1;
@@ -1504,8 +1534,6 @@ extern "C" int esgpu_plan_create(esgpu_ctx* c, const esgpu_agg_spec* specs, int3
                 require(is_bucket(pt) || pt == ESGPU_AGG_FILTER, ESGPU_ERR_INVALID, "metrics aggregations cannot have sub-aggregations");
                 p->specs[n.s.parent].children.push_back(i);
             }
-            if (n.s.type >= ESGPU_AGG_SUM && n.s.type <= ESGPU_AGG_VALUE_COUNT)
-                throw EsError(ESGPU_ERR_UNSUPPORTED, "sum/min/max/value_count run on the CPU path");
             if (n.s.type == ESGPU_AGG_TERMS) {
                 require(n.s.size >= 0 && n.s.min_doc_count >= 0, ESGPU_ERR_INVALID,
                         "parameters [requiredSize] and [minDocCount] must be >=0 in terms aggregation.");
@@ -1577,7 +1605,7 @@ extern "C" int esgpu_plan_create(esgpu_ctx* c, const esgpu_agg_spec* specs, int3
                     "]. Terms buckets can only be sorted on a sub-aggregator path that is built out of zero or more "
                     "single-bucket aggregations within the path and a final single-bucket or a metrics aggregation at the path end.");
             double probe;
-            if (t == ESGPU_AGG_AVG) {
+            if (t == ESGPU_AGG_AVG || is_single_value_metric(t)) {  // (InternalNumericMetricsAggregation.SingleValue)
                 require(key.empty() || key == "value", ESGPU_ERR_INVALID, "Invalid terms aggregation order path [" + n.order_path +
                         "]. Ordering on a single-value metrics aggregation can only be done on its value.");
             } else {
@@ -1812,6 +1840,7 @@ static const TermRanks* ensure_term_ranks(esgpu_ctx* c, const DevColumn* col, co
                                           hipStream_t st);
 static bool ranked_terms_on(const esgpu_ctx* c);
 static const DevColumn* terms_col(esgpu_plan* p, const esgpu_segment* s, const std::string& field);
+static const DevColumn* value_count_metric(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s);
 static const uint32_t* ensure_d32(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
 static const uint16_t* ensure_d16(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
 static const DevColumn* ensure_b16(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
@@ -2993,7 +3022,7 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
                         : pl.comp ? derive_comp_ords(p, pl, s) : terms_col(p, s, pl.ord_field);
     if (pl.comp && !oc) return 0;
     const DevColumn* hc = !HIST ? nullptr : pl.inner_terms ? terms_col(p, s, pl.hist_field) : s->col(pl.hist_field.c_str());
-    const DevColumn* mc = pl.met > 0 ? s->col(pl.metric_field.c_str()) : nullptr;
+    const DevColumn* mc = pl.vc_only ? value_count_metric(p, pl, s) : pl.met > 0 ? s->col(pl.metric_field.c_str()) : nullptr;
     const bool terms_outer = pl.outer == pl.term_spec;
     if (pl.inner_terms && pl.fresh) pl.deferred = false;
     if (pl.inner_terms && pl.can_defer && pl.fresh && oc && hc && oc->type == ESGPU_COL_ORD_U32 && hc->type == ESGPU_COL_ORD_U32 &&
@@ -3071,7 +3100,8 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
         }
         has_keys = true;
     }
-    const bool sparse_metric = pl.met > 0 && (!mc || mc->present.p || mc->multi);
+    // (a lone value_count's product is dense, and a segment lacking its field adds nothing to its sums)
+    const bool sparse_metric = pl.met > 0 && !pl.vc_only && (!mc || mc->present.p || mc->multi);
     // ords may be missing; a doc may have several keys: then the outer counts cannot be summed from the cells
     const bool inner_sparse = ORD && HIST && (inner_missing || pl.inner_terms ||
                                               (terms_outer ? (hc->present.p != nullptr || hc->multi) : true));
@@ -3087,7 +3117,7 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
         if (ORD && HIST) ocnt = inner_sparse ? (terms_outer ? OCNT_TERMS : OCNT_HIST) : OCNT_TERMS_DERIVED;
         // a reset plan keeps its buffers (already zeroed) when the new request's first segment has the same shape
         const bool same = pl.allocated && T == pl.T && H == pl.H && key0 == pl.key0 && vcnt == pl.vcnt_mode &&
-                          ocnt == pl.ocnt_mode;
+                          ocnt == pl.ocnt_mode && (!pl.vc_only || pl.met == 0 || pl.g_sum.p);
         pl.T = T;
         pl.H = H;
         pl.key0 = key0;
@@ -3207,7 +3237,9 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
         pl.dd_vals = 0;
         pl.dd_amax = 0;
     }
-    if (L_met > 0 && mc && !inner_missing) {
+    // (a pipeline whose leaves report no sum -- min / max / value_count beside each other -- keeps plain f64 adds: no
+    // low-part grids, no fold)
+    if (L_met > 0 && mc && !inner_missing && pl.sums) {
         pl.dd_vals += mc->multi ? mc->n_values : (uint64_t)s->max_doc;
         if (mc->type == ESGPU_COL_F64 || dd_forced()) {
             pl.dd = true;
@@ -3936,6 +3968,84 @@ static const uint16_t* ensure_d16(esgpu_ctx* c, const DevColumn* col, const esgp
     return m->d16.as<uint16_t>();
 }
 
+// ---- the per-doc value-count product (esgpu_valcount.hip) ----
+// How many values each doc of a column holds (ValueCountAggregator.collect adds values.count() per doc, A/metrics/
+// valuecount/ValueCountAggregator.java:75-88), as a dense single-valued long column that owns only its 16-bit deltas
+// (vmin 0, vmax the largest count): the collect loaders read it like any d16 metric and the cells' sums are exact.  Its
+// upload-width values start released (wide_i64 expands them for a kernel that reads 8-byte values).  Built on the
+// column's first use under the context lock and cached with it; it counts the segment's own values, so an ordinal map
+// built later leaves it as it is.  Over the HBM budget: ESGPU_ERR_OOM.  A doc with more than 65,535 values refuses the
+// request, and nothing is cached.  Null: the segment has no docs.
+static const DevColumn* ensure_value_counts(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st) {
+    DevColumn* m = const_cast<DevColumn*>(col);
+    if (s->n_pad == 0) return nullptr;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (m->vc_view) return m->vc_view.get();
+    std::unique_ptr<DevColumn> v(new DevColumn());
+    v->name = m->name;
+    v->type = ESGPU_COL_I64;
+    v->d16.alloc(c, (size_t)s->n_pad * 2);
+    unsigned int most = 1;
+    if (m->multi) {
+        DevBuf flag;
+        flag.alloc(c, 4);
+        HIPX(hipMemsetAsync(flag.p, 0, 4, st));
+        launch_value_counts_csr(m->off_view ? m->off_view : m->offsets.as<uint64_t>(), s->max_doc, s->n_pad, v->d16.as<uint16_t>(),
+                                flag.as<unsigned int>(), st);
+        HIPX(hipGetLastError());
+        HIPX(hipMemcpyAsync(&most, flag.p, 4, hipMemcpyDeviceToHost, st));
+    } else if (m->type == ESGPU_COL_ORD_U32) {
+        // (the 16-bit copy may hold global ordinals: missing stays missing under an ordinal map)
+        if (m->ord16.p) launch_value_counts_ord(m->ord16.p, 2, s->max_doc, s->n_pad, v->d16.as<uint16_t>(), st);
+        else launch_value_counts_ord(m->values.p, 4, s->max_doc, s->n_pad, v->d16.as<uint16_t>(), st);
+    } else if (m->present.p) {
+        launch_value_counts_present(m->present.as<uint64_t>(), s->max_doc, s->n_pad, v->d16.as<uint16_t>(), st);
+    } else {
+        launch_value_counts_ones(s->max_doc, s->n_pad, v->d16.as<uint16_t>(), st);
+    }
+    HIPX(hipGetLastError());
+    HIPX(hipStreamSynchronize(st));
+    require(most <= 65535u, ESGPU_ERR_UNSUPPORTED, "value_count over a field with more than 65,535 values in one doc runs on the CPU path");
+    v->vmin = 0;
+    v->vmax = (int64_t)most;
+    v->d16_done = v->d32_done = v->b16_done = v->hll32_done = true;  // (no other compact copy is ever built for it)
+    v->wide_released.store(true, std::memory_order_release);
+    m->vc_view = std::move(v);
+    return m->vc_view.get();
+}
+
+// the metric column of a pipeline of lone value_count leaves for this segment (Pipeline::vc_only): null while the doc
+// count is the value count, and for a segment lacking the field; else the field's value-count product
+static const DevColumn* value_count_metric(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s) {
+    if (pl.fresh) {  // a new request
+        pl.met = 0;
+        pl.vc_prod = false;
+    }
+    const DevColumn* src = s->col(pl.metric_field.c_str());
+    if (!pl.vc_prod) {
+        if (src && !src->multi && !src->present.p && src->type != ESGPU_COL_ORD_U32) return nullptr;
+        // the first segment whose value counts are not its doc counts: from here on the cells' sums count the values;
+        // the earlier segments' are the doc counts collected so far
+        const DevColumn* prod = src ? ensure_value_counts(p->ctx, src, s, p->stream) : nullptr;  // (may refuse: before any change)
+        // (a high-cardinality terms grid counted so far by the partitioned / hot-cold kernels keeps u32 counts, part of
+        // them pending in cold lists until the build: not seeded from)
+        const bool seed = !pl.fresh && pl.allocated;
+        require(!seed || !pl.cnt32, ESGPU_ERR_UNSUPPORTED,
+                "value_count over a field that turns sparse in a later segment under high-cardinality terms runs on the CPU path");
+        pl.vc_prod = true;
+        pl.met = 1;
+        if (seed) {
+            const size_t cells = (size_t)pl.T * pl.H;
+            zero_counts(p, pl);
+            if (!pl.g_sum.p || pl.g_sum.bytes < cells * 8) pl.g_sum.alloc(p->ctx, cells * 8 + cells * 2);
+            launch_counts_to_f64(pl.g_cnt.as<unsigned long long>(), cells, pl.g_sum.as<double>(), p->stream);
+            HIPX(hipGetLastError());
+        }
+        return prod;
+    }
+    return src ? ensure_value_counts(p->ctx, src, s, p->stream) : nullptr;
+}
+
 // ---- numeric ordinals (terms over long / date fields, LongTermsAggregator.java:78-107) ----
 // The segment's numeric dictionary -- the sorted distinct values of ALL its docs, whatever a request filters, as the
 // min_doc_count == 0 fill-in of the reference walks every doc of the reader (:113-125) -- and each doc's rank in it, as
@@ -4648,15 +4758,17 @@ static MetricCell metric_cell(const esgpu_plan* p, const Pipeline& pl, int j, si
     const HostCells& h = pl.hc;
     const uint64_t vc = pl.vcnt_mode ? h.vcnt[c] : h.cnt[c];
     MetricCell m{(int64_t)vc, 0.0, INFINITY, -INFINITY, 0.0};
-    if (vc > 0) {
+    if (vc > 0 && pl.met > 0) {  // (met 0: lone value_count leaves over dense columns, no metric cells)
         m.sum = h.sum[c];
-        if (pl.met >= 2 && type != ESGPU_AGG_AVG) {
+        if (pl.met >= 2 && metric_has_extrema(type)) {
             const uint64_t emn = h.mn[c], emx = h.mx[c];
             if (emn < kEncNegInf || emx > kEncPosInf) { m.min = NAN; m.max = NAN; }  // a NaN value was collected
             else { m.min = unsortable(emn); m.max = unsortable(emx); }
         }
         if (pl.met >= 3 && type == ESGPU_AGG_EXTENDED_STATS) m.sq = h.sq[c];
     }
+    // a lone value_count collected through the product: the cell's (exact, integer) sum of the per-doc counts
+    if (pl.vc_prod) m.count = h.sum ? (int64_t)h.sum[c] : 0;
     return m;
 }
 
@@ -5262,7 +5374,8 @@ static ReplaySel replay_child(esgpu_plan* p, const ChildSrc& kid, const std::vec
     const bool agg2 = tn2.s.order == ESGPU_ORDER_AGG_ASC || tn2.s.order == ESGPU_ORDER_AGG_DESC;
     const bool host_sel = agg2 || B0.value_count2 <= 65536;
     uint32_t wb = k;
-    if (!host_sel && kid.rpipes.size() == 1 && R0.met == 0 && R0.cards.empty()) {
+    // (a lone value_count leaf may still need its field's value counts collected: not a count-only child)
+    if (!host_sel && kid.rpipes.size() == 1 && R0.met == 0 && !R0.vc_only && R0.cards.empty()) {
         const uint64_t part_cells = (uint64_t)kPartMaxStaged << kPartShift;
         wb = (uint32_t)std::min<uint64_t>(k, std::max<uint64_t>(1, part_cells / replay_stride(B0.value_count2)));
         if (const char* e = std::getenv("ESGPU_REPLAY_BATCH")) {  // tests: smaller batches on small grids
@@ -5593,7 +5706,8 @@ static Block build_terms_root(esgpu_plan* p, const Group& g) {
                   kid.grand.size() <= (size_t)kCompactLeaves && kid.deep < 0;
         for (const LeafRef& l : kid.grand) {  // the leaves' grids index like B0's (the kernel reads one cell of each)
             const Pipeline& L = p->pipes[l.pipe];
-            ok = ok && L.allocated && L.H == B0.H && L.T == B0.T && L.key0 == B0.key0 &&
+            // (lone value_count leaves keep no sum cells, or count by them: read on the host)
+            ok = ok && L.allocated && L.H == B0.H && L.T == B0.T && L.key0 == B0.key0 && !L.vc_only &&
                  is_metric(p->specs[L.metrics[l.leaf]].s.type);
         }
         fast[ki] = ok;
@@ -5632,7 +5746,7 @@ static Block build_terms_root(esgpu_plan* p, const Group& g) {
             CompactLeaf& o = C.leaf[gj];
             o.cnt = (L.vcnt_mode ? L.g_vcnt : L.g_cnt).as<unsigned long long>();
             o.sum = L.g_sum.as<double>();
-            o.mn = L.met >= 2 && type != ESGPU_AGG_AVG ? L.g_min.as<unsigned long long>() : nullptr;
+            o.mn = L.met >= 2 && metric_has_extrema(type) ? L.g_min.as<unsigned long long>() : nullptr;
             o.mx = o.mn ? L.g_max.as<unsigned long long>() : nullptr;
             o.sq = L.met >= 3 && type == ESGPU_AGG_EXTENDED_STATS ? L.g_sq.as<double>() : nullptr;
             o.o_count = o.cnt == C.cnt ? nullptr : (uint32_t*)dev_at(2 + 5 * gj);
@@ -6310,7 +6424,7 @@ static bool colo_eligible(esgpu_plan* const* plans, int n, bool shape_only = fal
             !hn.tz_starts.empty() || (hn.s.order != ESGPU_ORDER_KEY_ASC && hn.s.order != ESGPU_ORDER_KEY_DESC))
             return false;
         for (const LeafRef& l : kid.grand)
-            if (!is_metric(p->specs[p->pipes[l.pipe].metrics[l.leaf]].s.type)) return false;
+            if (!is_metric(p->specs[p->pipes[l.pipe].metrics[l.leaf]].s.type) || p->pipes[l.pipe].vc_only) return false;
         if (shape_only) continue;
         const Pipeline& P0 = p->pipes[g.pipes[0]];
         const Pipeline& B0 = p->pipes[kid.pipes[0]];
@@ -6510,7 +6624,7 @@ static ColoShard colo_shard_desc(const esgpu_plan* p, int nl) {
         const unsigned long long* lc = (L.vcnt_mode ? L.g_vcnt : L.g_cnt).as<unsigned long long>();
         c.lcnt[l] = lc == c.cnt && !c.cnt32 ? nullptr : lc;
         c.lsum[l] = L.g_sum.as<double>();
-        c.lmn[l] = L.met >= 2 && type != ESGPU_AGG_AVG ? L.g_min.as<unsigned long long>() : nullptr;
+        c.lmn[l] = L.met >= 2 && metric_has_extrema(type) ? L.g_min.as<unsigned long long>() : nullptr;
         c.lmx[l] = c.lmn[l] ? L.g_max.as<unsigned long long>() : nullptr;
         c.lsq[l] = L.met >= 3 && type == ESGPU_AGG_EXTENDED_STATS ? L.g_sq.as<double>() : nullptr;
     }

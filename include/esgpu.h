@@ -115,6 +115,9 @@ int esgpu_ctx_get_option(const esgpu_ctx* ctx, int32_t option, int64_t* value);
  * Multi-valued columns are CSR: offsets[max_doc + 1] into values, values of one doc sorted ascending
  * (SortedNumericDocValues / SortedSetDocValues contract).  Single-valued numerics may carry a
  * `present` bitset (bit d set = doc d has a value); NULL = every doc has exactly one value.
+ * A value_count aggregation alone over a column of any type that is not dense and single-valued counts by the
+ * column's per-doc value counts: one u16 per doc (0 / 1 from a missing ordinal or the present bitset, the CSR offsets'
+ * differences), built on the device on the column's first use, cached with it and charged to the HBM budget.
  * ------------------------------------------------------------------------------------------------------- */
 enum {
     ESGPU_COL_ORD_U32 = 1,
@@ -219,6 +222,12 @@ enum {
     ESGPU_AGG_EXTENDED_STATS = 5,
     ESGPU_AGG_AVG = 6,
     ESGPU_AGG_CARDINALITY = 7,
+    /* single-value metrics (SumAggregator, MinAggregator, MaxAggregator, ValueCountAggregator): `field` is a long /
+     * date / double column -- for value_count any column, keyword and multi-valued ones included (it counts the
+     * field's values per doc, duplicates of a multi-valued numeric field too).  No sub-aggregations.  Result block:
+     * sum fills sum[i], min fills min[i], max fills max[i], value_count fills count[i]; the block's other metric arrays
+     * hold the empty aggregation's values (count 0, sum 0.0, min +Infinity, max -Infinity).  No doc with a value:
+     * 0.0 / +Infinity / -Infinity / 0.  A doc with more than 65,535 values of a value_count field: ESGPU_ERR_UNSUPPORTED. */
     ESGPU_AGG_SUM = 8,
     ESGPU_AGG_MIN = 9,
     ESGPU_AGG_MAX = 10,
@@ -240,7 +249,8 @@ enum {
     ESGPU_ORDER_HCOUNT_DESC = 7,
     /* terms ordered by a metric sub-aggregation (InternalOrder.Aggregation, A/bucket/terms/InternalOrder.java:149-225;
      * compound with _term asc tie-break; NaN values last, Comparators.compareDiscardNaN): esgpu_agg_spec.order_path
-     * names a direct stats / extended_stats / avg child, "<name>" or "<name>.value" for avg, "<name>.<metric>" for
+     * names a direct metric child, "<name>" or "<name>.value" for avg / sum / min / max / value_count (an empty bucket
+     * orders by 0 / +Infinity / -Infinity / 0 for the last four), "<name>.<metric>" for
      * stats (count, sum, min, max, avg) and extended_stats (+ sum_of_squares, variance, std_deviation, std_upper,
      * std_lower) -- AggregationPath.parse / validate (A/support/AggregationPath.java:68-113, 289-347) */
     ESGPU_ORDER_AGG_ASC = 8,
@@ -457,7 +467,9 @@ struct esgpu_agg_block {
     const int64_t* bucket_doc_count_errors; /* [n_buckets] */
     const esgpu_agg_block* subs;            /* nsubs blocks, each with n_instances == n_buckets */
     const esgpu_agg_block* empty_subs;      /* nsubs prototypes (n_instances == 1) for empty histogram buckets */
-    /* numeric metrics [n_instances] */
+    /* numeric metrics [n_instances]: stats / extended_stats fill all, avg count + sum; sum fills `sum`, min `min`, max
+     * `max`, value_count `count` (InternalSum / InternalMin / InternalMax / InternalValueCount hold that one value; the
+     * other arrays hold the empty aggregation's values) */
     const int64_t* count;
     const double* sum;
     const double* min;

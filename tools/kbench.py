@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """Kernel-level sweep: collect-kernel time and algorithmic GB/s for each §8 request shape on one synthetic shard.
 
-    python tools/kbench.py --docs 1000000000 --reps 5 [--only name,name]
+    python tools/kbench.py --docs 1000000000 --reps 5 [--only name,name] [--alternate]
 
 Prints one JSON line per variant: {"name", "kernel_ms", "bytes", "gbs", "frac", "path", "step_ms"}.
+--alternate runs the selected variants round-robin (rep 1 of each, rep 2 of each, ...) instead of one after the other, so
+that twins such as ns_sum / ns_avg share the device's state; each line then also carries kernel_ms_min / kernel_ms_max.
+The dh_sparse_* variants run on a second segment: @timestamp and a response_time_ms with a 60 % present bitset.
 """
 import argparse
 import json
@@ -36,6 +39,14 @@ def variants():
         "config1_terms_stats": ([AB.terms("hosts").field("host").subAggregation(AB.stats("rt").field("response_time_ms"))], None),
         "north_star": ([ns(AB.stats("rt").field("response_time_ms"))], None),
         "ns_avg": ([ns(AB.avg("rt").field("response_time_ms"))], None),
+        # the single-value twins: sum collects what avg collects, max what stats collects
+        "ns_sum": ([ns(AB.sum("rt").field("response_time_ms"))], None),
+        "ns_max": ([ns(AB.max("rt").field("response_time_ms"))], None),
+        # a lone value_count over a sparse column (its per-doc value-count product, 2 B per doc) against sum over it
+        "dh_sparse_count": ([AB.dateHistogram("h").field("@timestamp").interval("1h").subAggregation(
+            AB.count("rt").field("response_time_ms"))], None),
+        "dh_sparse_sum": ([AB.dateHistogram("h").field("@timestamp").interval("1h").subAggregation(
+            AB.sum("rt").field("response_time_ms"))], None),
         "config5": ([ns(AB.avg("rt").field("response_time_ms"))],
                     [QB.termQuery("status", 200), QB.rangeQuery("bytes").gte(1024).lte(65536)]),
         "config4_card": ([AB.cardinality("ips").field("client_ip.hash").precisionThreshold(40000)], None),
@@ -85,6 +96,20 @@ def _with_real_dicts(e, seg, n, fields):
     return e.upload_segment(cols, n)
 
 
+def _sparse_segment(e, seg, n):
+    """@timestamp and response_time_ms of `seg`, the latter present in 60 % of the docs"""
+    rng = np.random.default_rng(11)
+    present = rng.random(n) < 0.6
+    pad = np.zeros((n + 63) // 64 * 64, dtype=bool)
+    pad[:n] = present
+    bits = np.packbits(pad, bitorder="little").view(np.uint64)
+    rt = seg.read_column("response_time_ms", 0, n, np.int64)
+    rt[~present] = 0
+    cols = {"@timestamp": {"type": ea._native.COL_I64, "values": seg.read_column("@timestamp", 0, n, np.int64)},
+            "response_time_ms": {"type": ea._native.COL_I64, "values": rt, "present": bits}}
+    return e.upload_segment(cols, n)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=1_000_000_000)
@@ -96,6 +121,7 @@ def main():
     ap.add_argument("--deletes", type=float, default=0.0,
                     help="fraction of deleted docs: every request passes a live-docs accept bitset with that many random "
                          "docs cleared (Lucene liveDocs; the high-cardinality terms path then takes its scatter form)")
+    ap.add_argument("--alternate", action="store_true", help="run the selected variants round-robin instead of one after the other")
     ap.add_argument("--real-dict", action="store_true",
                     help="re-upload host/url as ordinary keyword columns with their term bytes (esgpu_segment_upload with a "
                          "dictionary), so the build resolves winners through a real 10M-term dictionary")
@@ -121,40 +147,62 @@ def main():
         accept = words
     print(json.dumps({"generated_s": time.time() - t, "hbm_gb": e.hbm_used() / 1e9, "ts_jitter_ms": args.ts_jitter,
                       "shards": args.shards, "deletes": args.deletes}), flush=True)
+    sparse = _sparse_segment(e, seg, args.docs) if any(k.startswith("dh_sparse_") for k in vs) else None
+    runs = {}
     for name, (aggs, flt) in vs.items():
-        plan = e.plan(aggs, filters=flt, number_of_shards=args.shards)
-        ms = []
-        steps = []
-        parts = {"reset": [], "collect_call": [], "kernel_wait": [], "build": [], "build_wait": [], "reduce": []}
-        for r in range(args.reps + 1):
-            t0 = time.perf_counter()
-            plan.reset()
-            t1 = time.perf_counter()
-            plan.collect(seg, accept_bits=accept)
-            t2 = time.perf_counter()
-            k, nbytes, path = plan.last_collect_stats()
-            t3 = time.perf_counter()
-            res = plan.build()
-            t4 = time.perf_counter()
-            bwait = plan.last_build_stats()[1]
-            ea.reduce([res])
-            t5 = time.perf_counter()
-            dt = (t5 - t0) * 1e3
-            if r:  # first is warmup
-                ms.append(k)
-                steps.append(dt)
-                for key, a, b in (("reset", t0, t1), ("collect_call", t1, t2), ("kernel_wait", t2, t3),
-                                  ("build", t3, t4), ("reduce", t4, t5)):
-                    parts[key].append((b - a) * 1e3)
-                parts["build_wait"].append(bwait)
+        runs[name] = {"plan": e.plan(aggs, filters=flt, number_of_shards=args.shards), "ms": [], "steps": [],
+                      "seg": sparse if name.startswith("dh_sparse_") else seg,
+                      "parts": {"reset": [], "collect_call": [], "kernel_wait": [], "build": [], "build_wait": [], "reduce": []}}
+
+    def one(name, r):
+        run = runs[name]
+        plan = run["plan"]
+        t0 = time.perf_counter()
+        plan.reset()
+        t1 = time.perf_counter()
+        plan.collect(run["seg"], accept_bits=accept)
+        t2 = time.perf_counter()
+        k, nbytes, path = plan.last_collect_stats()
+        t3 = time.perf_counter()
+        res = plan.build()
+        t4 = time.perf_counter()
+        bwait = plan.last_build_stats()[1]
+        ea.reduce([res])
+        t5 = time.perf_counter()
+        run["bytes"], run["path"] = nbytes, path
+        if r:  # first is warmup
+            run["ms"].append(k)
+            run["steps"].append((t5 - t0) * 1e3)
+            for key, a, b in (("reset", t0, t1), ("collect_call", t1, t2), ("kernel_wait", t2, t3),
+                              ("build", t3, t4), ("reduce", t4, t5)):
+                run["parts"][key].append((b - a) * 1e3)
+            run["parts"]["build_wait"].append(bwait)
+
+    def report(name):
+        run = runs[name]
+        ms, steps, nbytes = run["ms"], run["steps"], run["bytes"]
         kms = sorted(ms)[len(ms) // 2]
         gbs = nbytes / (kms / 1e3) / 1e9
-        print(json.dumps({"name": name, "ts_jitter_ms": args.ts_jitter, "deletes": args.deletes, "kernel_ms": round(kms, 4), "bytes": nbytes, "gbs": round(gbs, 1),
-                          "frac": round(gbs / 8000, 4), "path": path, "step_ms": round(sorted(steps)[len(steps) // 2], 3),
-                          "docs_per_s": args.docs / (kms / 1e3),
-                          "parts_ms": {k: round(sorted(v)[len(v) // 2], 3) for k, v in parts.items()}}), flush=True)
-        plan.close()
+        line = {"name": name, "ts_jitter_ms": args.ts_jitter, "deletes": args.deletes, "kernel_ms": round(kms, 4), "bytes": nbytes,
+                "gbs": round(gbs, 1), "frac": round(gbs / 8000, 4), "path": run["path"],
+                "step_ms": round(sorted(steps)[len(steps) // 2], 3), "docs_per_s": args.docs / (kms / 1e3),
+                "parts_ms": {k: round(sorted(v)[len(v) // 2], 3) for k, v in run["parts"].items()}}
+        if args.alternate:
+            line.update(kernel_ms_min=round(min(ms), 4), kernel_ms_max=round(max(ms), 4), alternated=True)
+        print(json.dumps(line), flush=True)
+        run["plan"].close()
 
+    if args.alternate:
+        for r in range(args.reps + 1):
+            for name in runs:
+                one(name, r)
+        for name in runs:
+            report(name)
+    else:
+        for name in runs:
+            for r in range(args.reps + 1):
+                one(name, r)
+            report(name)
 
 if __name__ == "__main__":
     main()
