@@ -291,6 +291,9 @@ def date_histogram_fixture(ref):
             "cite_fixture": f"{rel}:{_line_of(text, 'indexDoc(1, 2, 1)')}",
             "monthly": {"keys": [_utc("2012-01-01T00:00:00"), _utc("2012-02-01T00:00:00"), _utc("2012-03-01T00:00:00")],
                         "doc_counts": [1, 2, 3], "cite": f"{rel}:{_line_of(text, 'public void singleValuedField() throws Exception')}"},
+            # the multi-valued `dates` (each doc: its date and the day after, one month later): a doc counts once per key
+            "monthly_multi": {"keys": [_utc(f"2012-{m:02d}-01T00:00:00") for m in (1, 2, 3, 4)], "doc_counts": [1, 3, 5, 3],
+                              "cite": f"{rel}:{_line_of(text, 'public void multiValuedField() throws Exception')}"},
             "daily_tz_plus1": {"offset": -3600000, "min_doc_count": 1,
                                "keys": [_utc(s) for s in ["2012-01-01T23:00:00", "2012-02-01T23:00:00", "2012-02-14T23:00:00",
                                                            "2012-03-01T23:00:00", "2012-03-14T23:00:00", "2012-03-22T23:00:00"]],
