@@ -158,6 +158,32 @@ struct CollectParams {
     uint32_t n_chunks;
 };
 
+// The ranked kernel (esgpu_ranked.hip) reads only this of a path-10 collect: the 16-bit rank and metric-delta columns, the
+// block-delta key column, the zone keys, the packed-cell geometry and the grid.  Fields are CollectParams' of the same
+// name unless noted.
+struct RankedParams {
+    const uint16_t* rank16;  // each doc's frequency rank (CollectParams.ord16 of a ranked collect)
+    const uint16_t* mv16;
+    const uint16_t* hv16;
+    const int64_t* hv16_base;
+    const uint8_t* hv8;
+    const int64_t* zkey;
+    const uint32_t* rank_ord;
+    unsigned long long* g_cnt;
+    double* g_sum;
+    double* g_sum_lo;
+    unsigned long long* g_min;
+    unsigned long long* g_max;
+    int64_t mv_base, interval, offset, key0;
+    uint32_t hv8_mask, hv8_and;
+    uint32_t mg_m, mg_s1, mg_s2;  // magic division by interval (< 2^32)
+    uint32_t keys32;              // the most keys whose span, keys x interval, stays below 2^32
+    uint32_t K;                   // ranks collected (CollectParams.T)
+    uint32_t T_full, H, W, pk_shift, ncopies;
+    uint32_t cstride;             // > K * W: cell K * W of every copy is spare
+    uint32_t n_docs, n_blocks, blocks_per_wg;
+};
+
 enum HllKind : int32_t { HLL_I64 = 0, HLL_F64 = 1, HLL_ORD = 2 };
 
 struct HllParams {
@@ -365,6 +391,10 @@ size_t collect_lds_bytes(uint32_t T, uint32_t W, int met, int vcnt_mode, int ocn
                          uint32_t cstride = 0);  // cstride: CollectParams.cstride (packed cells)
 // resident workgroups per CU (hk: 0 none, 1 affine, 2 table; vk: bit 0 double histogram column, bit 1 double metric)
 int collect_occupancy(bool ord, int hk, int met, size_t lds, int vk, bool wide = false);
+// the ranked-terms collect over time-sorted block-delta keys (esgpu_ranked.hip): met 1 avg, 2 stats; grid = static
+// ranges of blocks_per_wg blocks; lds = collect_lds_bytes of the same packed cells
+void launch_ranked(const RankedParams& p, int met, uint32_t grid, size_t lds, hipStream_t s);
+int ranked_occupancy(int met, size_t lds);
 // returns whether the group floors and snapshot are left as lower bounds of the registers (HllParams.snap_ok for the
 // request's next segment)
 bool launch_hll(const HllParams& p, uint32_t cus, hipStream_t s);

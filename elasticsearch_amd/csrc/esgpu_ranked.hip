@@ -1,0 +1,288 @@
+// esgpu_ranked.hip — the ranked-terms collect (path 10) over 16-bit rank / metric-delta columns and block-delta keys of
+// time-sorted data: a kernel of its own for the one shape that path runs at, in place of the generic collect_kernel
+// (esgpu_collect.hpp), whose step loop carries multi-pass groups, the global-grid fallback, per-step prefetch scheduling
+// and the whole CollectParams block for shapes this path never sees.
+//
+// The unit of work is a zone block (kBlockDocs docs).  Its key range comes from the zone keys (zkey, a scalar load issued
+// one block ahead); the window decision and the choice between the two bodies are made once per block:
+//   - a full block whose docs all round to one key inside the grid (99.4 % of the north star's blocks at 1B docs) takes
+//     the unrolled body: 16 docs per thread in two buffers of 8, each reloaded for the next block right after it is
+//     processed, no key arithmetic, no tail mask, no per-step decision;
+//   - any other block (several keys, the segment's last partial block, a key outside the grid) takes the per-doc body,
+//     which loads the keys of the thread's 16 docs: docs inside the window go to the LDS cells, the rest to the grid by
+//     global atomics.  Correct for any data; it is not the fast path.
+// The LDS cells are collect_kernel's packed cells ([W keys][K ranks] count << pk_shift | sum of deltas in lane-rotated
+// copies cstride apart, and one (min, max) delta pair per cell), and the flush decodes them as flush_window_pi does.
+#include "esgpu_collect.hpp"
+
+namespace esgpu {
+
+#ifndef ESGPU_RK_WAVES  // waves per SIMD the register budget must allow (6: three 512-thread workgroups per CU)
+#define ESGPU_RK_WAVES 6
+#endif
+#ifndef ESGPU_RK_NT  // the two streamed columns by non-temporal loads (0: plain loads, for A/B builds)
+#define ESGPU_RK_NT 1
+#endif
+constexpr int kRkWG = 512;
+// The kernel's parameters again, for the code off the fast path (the flush, the per-doc body): read through this view,
+// a parameter is a scalar load where it is used.  Read through P, every parameter is loaded at the kernel's entry and
+// stays in an SGPR across the block loop, and the ~45 of them pushed 26 scalars into VGPR lanes, written and read back
+// in every block.  (RankedParams is the kernel's only argument: it starts the kernarg segment.  The empty asm keeps the
+// compiler from recognising the pointer and hoisting the loads back to the entry.)
+typedef const RankedParams __attribute__((address_space(4))) rk_params_c;
+__device__ __forceinline__ rk_params_c* rk_again() {
+    rk_params_c* q = (rk_params_c*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(q));
+    return q;
+}
+constexpr uint32_t kRkDocs = 8;                       // docs per thread per load (one 16-byte load per column)
+constexpr uint32_t kRkStepDocs = kRkWG * kRkDocs;     // 4,096
+static_assert(kBlockDocs == 2 * kRkStepDocs, "a zone block is two buffers of 8 docs per thread");
+
+__device__ __forceinline__ u32x4_t rk_load16(const uint16_t* p) {
+#if ESGPU_RK_NT
+    return __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
+#else
+    return load16(p);
+#endif
+}
+
+// 4 docs of a single-key block: their ranks (two words of 16-bit halves) and metric deltas.  `rowm` is the LDS address of
+// the block's row of (min, max) pairs, `dpk` the lane's distance from a pair to the packed word of the same cell in the
+// lane's copy, `missm` the pair of the spare cell (index K * W: never flushed, its pair (0, ~0) never moves), where the
+// docs whose rank is not collected go -- so every lane issues the same straight-line LDS traffic: 4 pair reads, then 4
+// adds, one wait for the reads; the bound atomics only where a bound moves.  MET 1 (avg): no pairs -- `rowm` / `missm`
+// then address the packed words of the lane's copy themselves and dpk is 0.
+template <int MET>
+__device__ __forceinline__ void rk_quad(uint32_t r0, uint32_t r1, uint32_t m0, uint32_t m1, uint32_t K, uint32_t rowm,
+                                        uint32_t missm, uint32_t dpk, uint32_t onehi) {
+    const uint32_t t[4] = {r0 & 0xFFFFu, r0 >> 16, r1 & 0xFFFFu, r1 >> 16};
+    const uint32_t dv[4] = {m0 & 0xFFFFu, m0 >> 16, m1 & 0xFFFFu, m1 >> 16};
+    uint32_t ca[4], mlo[4], mhi[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {  // (a rank past K, the missing rank 0xFFFF included, is not collected)
+        ca[j] = t[j] < K ? rowm + 8u * t[j] : missm;
+        if constexpr (MET >= 2) {
+            const u32x2_t m = *lds_ptr<u32x2_t>(ca[j]);
+            mlo[j] = m.x;
+            mhi[j] = m.y;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)  // pk_shift >= 33: the packed add is the pair {delta, 1 << (pk_shift - 32)}
+        atomicAdd(lds_ptr<unsigned long long>(ca[j] + dpk), join64(dv[j], onehi));
+    if constexpr (MET >= 2) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if ((dv[j] < mlo[j]) | (dv[j] > mhi[j])) {
+                atomicMin(lds_ptr<uint32_t>(ca[j]), dv[j]);
+                atomicMax(lds_ptr<uint32_t>(ca[j] + 4u), dv[j]);
+            }
+        }
+    }
+}
+
+template <int MET>
+__global__ __launch_bounds__(kRkWG, ESGPU_RK_WAVES) void ranked_kernel(RankedParams P) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const uint32_t K = P.K, W = P.W, C = K * W;
+    const uint32_t ncp = max(P.ncopies, 1u);
+    const uint32_t CS = P.cstride;  // > C: cell C of every copy is spare
+    // the carve of collect_kernel's packed cells (collect_lds_bytes(pi = true)); the pair of the spare cell lies in what
+    // is there the threads' spare words
+    unsigned long long* const pk = (unsigned long long*)smem;
+    uint32_t* const mm = (uint32_t*)(smem + ((8 * (size_t)CS * ncp + 15) & ~(size_t)15));
+    const uint32_t coff = ((threadIdx.x & 63) % ncp) * CS;
+    for (uint32_t c = threadIdx.x; c < CS * ncp; c += kRkWG) pk[c] = 0;
+    if constexpr (MET >= 2) {
+        for (uint32_t c = threadIdx.x; c < C; c += kRkWG) { mm[2 * c] = ~0u; mm[2 * c + 1] = 0u; }
+        if (threadIdx.x == 0) { mm[2 * C] = 0u; mm[2 * C + 1] = ~0u; }
+    }
+    __syncthreads();
+
+    const uint32_t b_begin = blockIdx.x * P.blocks_per_wg;
+    const uint32_t b_end = min(b_begin + P.blocks_per_wg, P.n_blocks);
+    if (b_begin >= b_end) return;
+
+    const uint32_t sh = P.pk_shift;
+    const uint32_t onehi = 1u << (sh - 32);
+    // LDS addresses of the fast body (rk_quad)
+    const uint32_t cell0 = MET >= 2 ? lds_addr(mm) : lds_addr(pk + coff);
+    const uint32_t missm = cell0 + 8u * C;
+    const uint32_t dpk = MET >= 2 ? lds_addr(pk + coff) - lds_addr(mm) : 0u;
+
+    uint32_t win0 = 0;
+    bool win_set = false, dirty = false;
+
+    // the window's cells into the grid, as flush_window_pi: exact integer sums (count * base + sum of deltas; compensated
+    // when g_sum_lo is set), order-preserving extrema, a cell's words read and reset before its atomics are issued
+    auto flush = [&]() {
+        const auto& Q = *rk_again();
+        __syncthreads();
+        const unsigned long long mask = (1ull << sh) - 1ull;
+        for (uint32_t c = threadIdx.x; c < C; c += kRkWG) {
+            unsigned long long n = 0;
+            for (uint32_t k = 0; k < ncp; ++k) n += pk[k * CS + c];
+            if (n == 0) continue;
+            const uint32_t local = c / K;
+            const uint32_t t = c - local * K;
+            const uint32_t slot = win0 + local;
+            if (slot >= Q.H) continue;
+            const size_t g = (size_t)slot * Q.T_full + Q.rank_ord[t];
+            const unsigned long long cnt = n >> sh;
+            uint32_t lo = 0, hi = 0;
+            if constexpr (MET >= 2) {
+                const u32x2_t m = *reinterpret_cast<const u32x2_t*>(mm + 2 * c);
+                lo = m.x;
+                hi = m.y;
+                u32x2_t r;
+                r.x = ~0u;
+                r.y = 0u;
+                *reinterpret_cast<u32x2_t*>(mm + 2 * c) = r;
+            }
+            atomicAdd(&Q.g_cnt[g], cnt);
+            for (uint32_t k = 0; k < ncp; ++k) pk[k * CS + c] = 0;
+            const long long isum = (long long)(n & mask) + (long long)cnt * Q.mv_base;
+            if (Q.g_sum_lo) {
+                double xh, xl;
+                i64_to_dd(isum, xh, xl);
+                dd_atomic_add(&Q.g_sum[g], Q.g_sum_lo + g, xh, xl);
+            } else {
+                atomicAdd(&Q.g_sum[g], (double)isum);
+            }
+            if constexpr (MET >= 2) {
+                atomicMin(&Q.g_min[g], sortable((double)(Q.mv_base + (int64_t)lo)));
+                atomicMax(&Q.g_max[g], sortable((double)(Q.mv_base + (int64_t)hi)));
+            }
+        }
+        __syncthreads();
+    };
+    auto slide_to = [&](uint32_t k0) {
+        if (dirty) flush();
+        dirty = false;
+        win0 = k0;
+        win_set = true;
+    };
+
+    // any block, doc by doc: 4 docs of the thread (docs doc0 .. doc0 + 3, their rank and metric words as the block's
+    // buffers hold them -- the columns are not read again) with their keys by the block-delta unpack, slots by the magic
+    // division of the value's distance from the block's first key (the zone map bounds the block's values, so the
+    // distance is non-negative and below the block's keys x interval; a block spanning 2^32 or more divides in 64 bits)
+    auto slow_quad = [&](uint32_t doc0, uint32_t r0, uint32_t r1, uint32_t m0, uint32_t m1, int64_t kmn, int64_t kmx) {
+        const auto& Q = *rk_again();
+        const int64_t vb = (Q.key0 + kmn) * Q.interval + Q.offset;  // the first instant of key kmn
+        const bool d32 = kmx - kmn < (int64_t)Q.keys32;            // the block's keys x interval < 2^32
+        const uint32_t wn = win_set ? W : 0u;
+        if (doc0 < Q.n_docs) {
+            const uint32_t nd = min(Q.n_docs - doc0, 4u);
+            const u32x2_t tw = load8(Q.hv16 + doc0);
+            const uint32_t hb = *reinterpret_cast<const uint32_t*>(Q.hv8 + (doc0 & Q.hv8_mask)) & (Q.hv8_and * 0x01010101u);
+            const u32x2_t bw = load8(Q.hv16_base + (doc0 >> kB16Shift));
+            const int64_t b = (int64_t)join64(bw.x, bw.y);
+#pragma unroll 1
+            for (uint32_t j = 0; j < nd; ++j) {
+                const uint32_t r2 = j < 2 ? r0 : r1, m2 = j < 2 ? m0 : m1, t2 = j < 2 ? tw.x : tw.y;
+                const uint32_t hs = (j & 1u) * 16u;
+                const uint32_t t = (r2 >> hs) & 0xFFFFu, dv = (m2 >> hs) & 0xFFFFu;
+                if (t >= K) continue;
+                const int64_t v = b + (int64_t)(((t2 >> hs) & 0xFFFFu) | (((hb >> (8u * j)) & 0xFFu) << 16));
+                const int64_t k = d32 ? kmn + (int64_t)magic_div((uint32_t)((uint64_t)v - (uint64_t)vb), Q.mg_m, Q.mg_s1,
+                                                                 Q.mg_s2, (uint32_t)Q.interval)
+                                      : floor_div64(v - Q.offset, Q.interval) - Q.key0;
+                if ((uint64_t)k >= (uint64_t)Q.H) continue;
+                const uint32_t sl = (uint32_t)k - win0;
+                if (sl < wn) {
+                    const uint32_t c = sl * K + t;
+                    atomicAdd(&pk[c + coff], (1ull << sh) + dv);
+                    if constexpr (MET >= 2) {
+                        const u32x2_t m = *reinterpret_cast<const u32x2_t*>(mm + 2 * c);
+                        if ((dv < m.x) | (dv > m.y)) {
+                            atomicMin(&mm[2 * c], dv);
+                            atomicMax(&mm[2 * c + 1], dv);
+                        }
+                    }
+                } else {  // outside the window: the doc's grid cell, as the generic kernel's global-grid path
+                    const size_t g = (size_t)k * Q.T_full + Q.rank_ord[t];
+                    atomicAdd(&Q.g_cnt[g], 1ull);
+                    const double x = (double)(Q.mv_base + (int64_t)dv);
+                    dd_atomic_add(&Q.g_sum[g], Q.g_sum_lo ? Q.g_sum_lo + g : nullptr, x);
+                    if constexpr (MET >= 2) {
+                        const unsigned long long e = sortable(x);
+                        if (e < Q.g_min[g]) atomicMin(&Q.g_min[g], e);
+                        if (e > Q.g_max[g]) atomicMax(&Q.g_max[g], e);
+                    }
+                }
+            }
+        }
+    };
+
+    // Software pipeline over the block's two buffers.  The two columns are streamed once and never read again, so
+    // their loads are non-temporal: they do not displace the grid, the zone keys and the rank table in L2 / MALL (north
+    // star at 1B docs 0.730 -> 0.655 ms per step with them).  Loads are unconditional and no loaded register
+    // is copied, as in collect_kernel.  The zone keys are
+    // read through zkey_view (scalar loads), a block ahead.
+    const zkey_pair_c* const zk = zkey_view(P.zkey);
+    const uint32_t tid8 = threadIdx.x * kRkDocs;
+    i64x2_t z = zk[__builtin_amdgcn_readfirstlane(b_begin)];
+    u32x4_t ra = rk_load16(P.rank16 + (size_t)b_begin * kBlockDocs + tid8);
+    u32x4_t ma = rk_load16(P.mv16 + (size_t)b_begin * kBlockDocs + tid8);
+    u32x4_t rb = rk_load16(P.rank16 + (size_t)b_begin * kBlockDocs + kRkStepDocs + tid8);
+    u32x4_t mb = rk_load16(P.mv16 + (size_t)b_begin * kBlockDocs + kRkStepDocs + tid8);
+#pragma unroll 1
+    for (uint32_t cb = b_begin; cb < b_end; ++cb) {
+        const int64_t kmn = z.x, kmx = z.y;
+        const uint32_t nb = __builtin_amdgcn_readfirstlane(min(cb + 1, b_end - 1));
+        z = zk[nb];
+        // (past the range's end the loads stay, but every lane reads the columns' first words: one cached line instead
+        // of the last block streamed again, which the non-temporal loads would fetch from HBM a second time -- with
+        // ranges of 32 blocks that was 1.5 % of traffic)
+        const bool more = cb + 1 < b_end;
+        const size_t nd0 = more ? (size_t)nb * kBlockDocs + tid8 : 0, nd1 = more ? nd0 + kRkStepDocs : 0;
+        // (every lane reads the same zone keys: the decisions are uniform over the workgroup)
+        const bool any = kmn <= kmx && kmx >= 0 && kmn < (int64_t)P.H;  // some doc of the block may lie in the grid
+        if (any) {
+            const bool fits = kmx - kmn < (int64_t)W;
+            if (!win_set || (fits && (kmn < (int64_t)win0 || kmx >= (int64_t)win0 + (int64_t)W)))
+                slide_to((uint32_t)min(max(kmn, (int64_t)0), (int64_t)P.H - 1));
+        }
+        const bool fast = kmn == kmx && (uint64_t)kmn < (uint64_t)P.H && (uint64_t)(cb + 1) * kBlockDocs <= P.n_docs;
+        if (!fast && any) {
+            const uint32_t d0 = cb * kBlockDocs + tid8;
+            slow_quad(d0, ra.x, ra.y, ma.x, ma.y, kmn, kmx);
+            slow_quad(d0 + 4u, ra.z, ra.w, ma.z, ma.w, kmn, kmx);
+            slow_quad(d0 + kRkStepDocs, rb.x, rb.y, mb.x, mb.y, kmn, kmx);
+            slow_quad(d0 + kRkStepDocs + 4u, rb.z, rb.w, mb.z, mb.w, kmn, kmx);
+        }
+        dirty = dirty || any;
+        // each buffer has one reload per block, outside the branches: a reload under a branch gives the buffer two
+        // definitions, which the compiler joins by copying the loaded registers -- a vmcnt(0) wait per block
+        const uint32_t rowm = cell0 + 8u * (((uint32_t)kmn - win0) * K);
+        if (fast) {
+            rk_quad<MET>(ra.x, ra.y, ma.x, ma.y, K, rowm, missm, dpk, onehi);
+            rk_quad<MET>(ra.z, ra.w, ma.z, ma.w, K, rowm, missm, dpk, onehi);
+        }
+        ra = rk_load16(P.rank16 + nd0);
+        ma = rk_load16(P.mv16 + nd0);
+        if (fast) {
+            rk_quad<MET>(rb.x, rb.y, mb.x, mb.y, K, rowm, missm, dpk, onehi);
+            rk_quad<MET>(rb.z, rb.w, mb.z, mb.w, K, rowm, missm, dpk, onehi);
+        }
+        rb = rk_load16(P.rank16 + nd1);
+        mb = rk_load16(P.mv16 + nd1);
+    }
+    if (dirty) flush();
+}
+
+void launch_ranked(const RankedParams& p, int met, uint32_t grid, size_t lds, hipStream_t st) {
+    if (met >= 2) hipLaunchKernelGGL(ranked_kernel<2>, dim3(grid), dim3(kRkWG), lds, st, p);
+    else hipLaunchKernelGGL(ranked_kernel<1>, dim3(grid), dim3(kRkWG), lds, st, p);
+}
+
+int ranked_occupancy(int met, size_t lds) {
+    int n = 0;
+    const hipError_t e = met >= 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ranked_kernel<2>, kRkWG, lds)
+                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ranked_kernel<1>, kRkWG, lds);
+    return e == hipSuccess ? n : 1;
+}
+
+}  // namespace esgpu

@@ -89,6 +89,11 @@ extern "C" int esgpu_ctx_set_option(esgpu_ctx* c, int32_t option, int64_t value)
             c->opt_num_max = value;
             return;
         }
+        if (option == ESGPU_OPT_RANKED_TERMS) {  // (2: path 10 on the generic collect kernel)
+            require(value >= 0 && value <= 2, ESGPU_ERR_INVALID, "ranked terms option must be 0..2");
+            c->opt_ranked = (int)value;
+            return;
+        }
         require(value == 0 || value == 1, ESGPU_ERR_INVALID, "option value must be 0 or 1");
         if (option == ESGPU_OPT_COMPACT_COLUMNS) c->opt_compact = (int)value;
         else if (option == ESGPU_OPT_PACKED_METRIC) c->opt_pi = (int)value;
@@ -1165,6 +1170,7 @@ struct esgpu_plan {
     bool collected = false, posted = false;
     double last_ms = 0;
     uint64_t last_bytes = 0;
+    int32_t last_kernel = 0;  // the last collect's LDS-window kernel: 0 collect_kernel, 1 ranked_kernel (esgpu_ranked.hip)
     double b_wait = 0, b_total = 0;  // last build: stream waits / whole call (ms)
     bool b_trace = false;
     std::vector<std::pair<const char*, double>> b_marks;
@@ -3559,14 +3565,22 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
     P.ukey32 = L_HIST && !P.hv16 && P.hv32 && ((pi && P.ord16 && P.mv16) || P.raw_dense) && !P.kstart && hc &&
                pl.interval > 0 && hc->zspan < pl.interval ? 1 : 0;
     P.rank_cells = rk && rkc && P.hv16 && !fold ? 1 : 0;
+    // The ranked kernel (esgpu_ranked.hip) in place of collect_kernel: a ranked collect of avg / stats leaves over the
+    // 16-bit metric deltas and block-delta keys whose typical block lies inside one key (zspan: the statistic the window
+    // choice uses), in packed cells with lane-rotated copies (each copy then has a spare cell past the window's, where
+    // the kernel sends the docs it does not collect).  Its per-doc body divides by the interval in 32 bits.
+    // ESGPU_OPT_RANKED_TERMS = 2 keeps path 10 on collect_kernel.
+    const bool rkk = rk && p->ctx->opt_ranked.load() == 1 && pi && P.lds_mode && L_HIST && P.hv16 && P.mv16 && !fold && !wide &&
+                     !L_vcnt && (L_met == 1 || L_met == 2) && P.ncopies > 1 && P.cstride > LK * W && !P.kstart && !P.hord && hc &&
+                     pl.interval > 0 && pl.interval < (1ll << 32) && hc->zspan < pl.interval && !dyn_claim_on();
     const int vk = (P.hv_f64 ? 1 : 0) | (P.mv_f64 ? 2 : 0) | (P.ord_src ? 8 : 0) | (P.ord16 ? 16 : 0) | (P.hv32 ? 32 : 0) |
                    (pi ? 64 : 0) | (m32 ? 128 : 0) | (P.mv16 ? 256 : 0) | (fold ? 512 : 0) | (P.raw_dense ? 1024 : 0) |
                    (P.runs1 ? 4096 : 0) | (P.hv16 ? 8192 : 0) | (P.ukey32 ? 16384 : 0) |
                    (P.ocnt_mode != OCNT_TERMS && P.ocnt_mode != OCNT_HIST ? 32768 : 0) | (P.rank_cells ? 65536 : 0);
     const uint64_t occ_key = ((uint64_t)lds << 24) | ((uint64_t)wide << 23) | ((uint64_t)vk << 8) | ((uint64_t)L_met << 4) |
-                             ((uint64_t)hk << 1) | (L_ORD ? 1 : 0);
+                             ((uint64_t)hk << 1) | (L_ORD ? 1 : 0) | (rkk ? 1ull << 63 : 0);
     if (pl.occ_key != occ_key) {
-        pl.occ = std::max(1, collect_occupancy(L_ORD, hk, L_met, lds, vk, wide));
+        pl.occ = std::max(1, rkk ? ranked_occupancy(L_met, lds) : collect_occupancy(L_ORD, hk, L_met, lds, vk, wide));
         pl.occ_key = occ_key;
     }
     const uint32_t wg_per_cu = (uint32_t)pl.occ;
@@ -3661,10 +3675,48 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
     }
     zero_counts(p, pl);
     if (rk) HIPX(hipMemcpyAsync(pl.g_ocnt.p, rk->counts.p, (size_t)pl.T * 8, hipMemcpyDeviceToDevice, p->stream));
-    launch_collect(P, L_ORD, L_HIST, L_met, wide, grid, lds, p->stream);
+    if (rkk) {
+        require(!P.claim && P.zkey, ESGPU_ERR_DEVICE, "internal: ranked kernel without static ranges or zone keys");
+        RankedParams R{};
+        R.rank16 = P.ord16;
+        R.mv16 = P.mv16;
+        R.hv16 = P.hv16;
+        R.hv16_base = P.hv16_base;
+        R.hv8 = P.hv8;
+        R.hv8_mask = P.hv8_mask;
+        R.hv8_and = P.hv8_and;
+        R.zkey = P.zkey;
+        R.rank_ord = P.rank_ord;
+        R.g_cnt = P.g_cnt;
+        R.g_sum = P.g_sum;
+        R.g_sum_lo = P.g_sum_lo;
+        R.g_min = P.g_min;
+        R.g_max = P.g_max;
+        R.mv_base = P.mv_base;
+        R.interval = P.interval;
+        R.offset = P.offset;
+        R.key0 = P.key0;
+        const MagicU32 mg = make_magic((uint32_t)pl.interval);
+        R.mg_m = mg.m; R.mg_s1 = mg.s1; R.mg_s2 = mg.s2;
+        R.keys32 = (uint32_t)(0xFFFFFFFFull / (uint64_t)pl.interval);
+        R.K = P.T;
+        R.T_full = P.T_full;
+        R.H = P.H;
+        R.W = P.W;
+        R.pk_shift = P.pk_shift;
+        R.ncopies = P.ncopies;
+        R.cstride = P.cstride;
+        R.n_docs = P.n_docs;
+        R.n_blocks = P.n_blocks;
+        R.blocks_per_wg = P.blocks_per_wg;
+        launch_ranked(R, L_met, grid, lds, p->stream);
+    } else {
+        launch_collect(P, L_ORD, L_HIST, L_met, wide, grid, lds, p->stream);
+    }
     HIPX(hipGetLastError());
     HIPX(hipEventRecord(pl.e1, p->stream));
     dd_fold();
+    p->last_kernel = rkk ? 1 : 0;
     p->last_bytes += bytes_per_doc * (uint64_t)s->max_doc + (d_accept ? ((uint64_t)s->max_doc + 7) / 8 : 0) +
                      (P.hv16 ? (((uint64_t)s->max_doc + kB16Docs - 1) >> kB16Shift) * 8 : 0);
     p->last_path = rk ? 10 : P.lds_mode ? (P.windowed ? 2 : 1) : 0;
@@ -4400,6 +4452,7 @@ extern "C" int esgpu_plan_collect_segment(esgpu_plan* p, const esgpu_segment* s,
         }
         p->last_bytes = 0;
         p->last_ms = -1;
+        p->last_kernel = 0;
         p->zu_n = 0;
         bool deferred = false, ranked = false;
         for (Pipeline& pl : p->pipes) {
@@ -4484,6 +4537,13 @@ extern "C" int esgpu_plan_last_collect_stats(const esgpu_plan* cp, double* kerne
         if (kernel_ms) *kernel_ms = p->last_ms;
         if (bytes) *bytes = p->last_bytes;
         if (path) *path = p->last_path;
+    });
+}
+
+extern "C" int esgpu_plan_last_collect_kernel(const esgpu_plan* cp, int32_t* id) {
+    return guarded([&] {
+        require(cp != nullptr && id != nullptr, ESGPU_ERR_INVALID, "null argument");
+        *id = cp->last_kernel;
     });
 }
 

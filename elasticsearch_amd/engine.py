@@ -230,6 +230,12 @@ class Plan:
         N.check(N.lib().esgpu_plan_last_collect_stats(self._ptr, ctypes.byref(ms), ctypes.byref(nbytes), ctypes.byref(path)))
         return ms.value, nbytes.value, path.value
 
+    def last_collect_kernel(self):
+        """0: the generic collect kernel ran the last collect, 1: the ranked kernel"""
+        kid = ctypes.c_int32()
+        N.check(N.lib().esgpu_plan_last_collect_kernel(self._ptr, ctypes.byref(kid)))
+        return kid.value
+
     def last_build_stats(self):
         """(total_ms, stream_wait_ms) of the last build()"""
         tot, wait = ctypes.c_double(), ctypes.c_double()
@@ -284,7 +290,7 @@ class Engine:
 
     def set_option(self, name, value):
         """Layout option of this context (esgpu_ctx_set_option): 'compact_columns' / 'packed_metric' / 'block_deltas' /
-        'ranked_terms', 0 or 1;
+        0 or 1; 'ranked_terms' 0, 1 or 2 (2: path 10 on the generic collect kernel instead of the ranked kernel);
         'hll_floor' 0..8 (include/esgpu.h ESGPU_OPT_HLL_FLOOR); 'numeric_terms_max_distinct': the distinct values of a long field
         in one segment above which terms over it are refused (default 2^22)."""
         N.check(N.lib().esgpu_ctx_set_option(self._ptr, self.OPTIONS[name], int(value)))

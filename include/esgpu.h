@@ -86,8 +86,10 @@ int esgpu_device_count(int* count);
  *   ESGPU_OPT_RANKED_TERMS:    an unfiltered top-level terms aggregation in count order over a shard's only segment
  *                              collects its sub-aggregations for the top shard_size terms alone, known beforehand from
  *                              the segment's term counts (the reference's breadth_first collect mode with the counting
- *                              pass cached per segment).  0 collects every term.  Not read from the
- *                              environment.
+ *                              pass cached per segment).  0 collects every term; 1 (the default) runs the
+ *                              collect on the ranked kernel where the shape allows (stats / avg over 16-bit metric
+ *                              deltas, block-delta keys of time-sorted data), 2 always on the generic collect kernel.
+ *                              Not read from the environment.
  * and one limit:
  *   ESGPU_OPT_NUMERIC_TERMS_MAX_DISTINCT: terms over a long / date field count by the segment's numeric ordinals; a
  *                              segment with more distinct values than this (default 2^22) is refused with
@@ -408,6 +410,9 @@ int esgpu_plan_destroy(esgpu_plan* plan);
  * is retained -- esgpu_plan_deferred_segments -- and collected again over every term if the request brings a second). */
 int esgpu_plan_last_collect_stats(const esgpu_plan* plan, double* kernel_ms, uint64_t* algorithmic_bytes,
                                   int32_t* path);
+/* The kernel that ran the last collect's LDS-window launch: 0 the generic collect kernel, 1 the ranked kernel (path 10
+ * where ESGPU_OPT_RANKED_TERMS = 1 and the shape allows). */
+int esgpu_plan_last_collect_kernel(const esgpu_plan* plan, int32_t* id);
 /* Wall time of the last esgpu_plan_build and the part of it spent waiting on the plan's stream (gathers and copies of
  * the winners' cells); the rest is host assembly of the result blocks.  Milliseconds. */
 int esgpu_plan_last_build_stats(const esgpu_plan* plan, double* total_ms, double* wait_ms);
