@@ -164,6 +164,7 @@ SIGNATURES = [
     ("esgpu_plan_last_collect_stats", ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64),
                                                      ctypes.POINTER(ctypes.c_int32)]),
     ("esgpu_plan_last_collect_kernel", ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_int32)]),
+    ("esgpu_plan_last_collect_read_bytes", ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_uint64)]),
     ("esgpu_plan_last_build_stats", ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     ("esgpu_plan_shard_mergeable", ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_int32)]),
     ("esgpu_plan_deferred_segments", ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_int32)]),

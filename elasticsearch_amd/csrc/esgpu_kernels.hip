@@ -1705,6 +1705,27 @@ __global__ void rank_ord16_kernel(const uint16_t* src, uint32_t n, const uint16_
 void launch_rank_ord16(const uint16_t* ord16, uint32_t n, const uint16_t* rank_of, uint32_t T, uint16_t* out, hipStream_t st) {
     if (n) hipLaunchKernelGGL(rank_ord16_kernel, dim3(std::min<uint32_t>(8192, (n + 255) / 256)), dim3(256), 0, st, ord16, n, rank_of, T, out);
 }
+// rank8 (TermRanks): 8 ranks per thread, one 16-byte load and one 8-byte store; n is a multiple of 8 (n_pad)
+__global__ void rank8_kernel(const uint16_t* src, uint32_t n8, uint8_t* out) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += gridDim.x * blockDim.x) {
+        const u32x4_t v = load16(src + (size_t)i * 8);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        uint32_t b[8];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            b[2 * j] = min(w[j] & 0xFFFFu, 255u);
+            b[2 * j + 1] = min(w[j] >> 16, 255u);
+        }
+        u32x2_t o;
+        o.x = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+        o.y = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
+        *reinterpret_cast<u32x2_t*>(out + (size_t)i * 8) = o;
+    }
+}
+void launch_rank8(const uint16_t* rank16, uint32_t n, uint8_t* out, hipStream_t st) {
+    const uint32_t n8 = n / 8;
+    if (n8) hipLaunchKernelGGL(rank8_kernel, dim3(std::min<uint32_t>(8192, (n8 + 255) / 256)), dim3(256), 0, st, rank16, n8, out);
+}
 __global__ void delta32_kernel(const int64_t* v, uint32_t n, int64_t base, uint32_t* out) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
         out[i] = (uint32_t)((uint64_t)v[i] - (uint64_t)base);

@@ -158,11 +158,12 @@ struct CollectParams {
     uint32_t n_chunks;
 };
 
-// The ranked kernel (esgpu_ranked.hip) reads only this of a path-10 collect: the 16-bit rank and metric-delta columns, the
+// The ranked kernel (esgpu_ranked.hip) reads only this of a path-10 collect: the rank and 16-bit metric-delta columns, the
 // block-delta key column, the zone keys, the packed-cell geometry and the grid.  Fields are CollectParams' of the same
 // name unless noted.
 struct RankedParams {
-    const uint16_t* rank16;  // each doc's frequency rank (CollectParams.ord16 of a ranked collect)
+    const void* rank;  // each doc's frequency rank: TermRanks' rank8 (one byte, 0xFF = rank >= 255 or missing) or rank16
+                       // (CollectParams.ord16 of a ranked collect), as the launch's rank width says
     const uint16_t* mv16;
     const uint16_t* hv16;
     const int64_t* hv16_base;
@@ -393,8 +394,9 @@ size_t collect_lds_bytes(uint32_t T, uint32_t W, int met, int vcnt_mode, int ocn
 int collect_occupancy(bool ord, int hk, int met, size_t lds, int vk, bool wide = false);
 // the ranked-terms collect over time-sorted block-delta keys (esgpu_ranked.hip): met 1 avg, 2 stats; grid = static
 // ranges of blocks_per_wg blocks; lds = collect_lds_bytes of the same packed cells
-void launch_ranked(const RankedParams& p, int met, uint32_t grid, size_t lds, hipStream_t s);
-int ranked_occupancy(int met, size_t lds);
+// rw: bytes per rank (1: RankedParams.rank is rank8, 2: rank16)
+void launch_ranked(const RankedParams& p, int met, int rw, uint32_t grid, size_t lds, hipStream_t s);
+int ranked_occupancy(int met, int rw, size_t lds);
 // returns whether the group floors and snapshot are left as lower bounds of the registers (HllParams.snap_ok for the
 // request's next segment)
 bool launch_hll(const HllParams& p, uint32_t cus, hipStream_t s);
@@ -454,6 +456,8 @@ void launch_narrow_u64(const unsigned long long* src, size_t n, unsigned int* ds
 void launch_pack_ord16(const uint32_t* src, uint32_t n, uint16_t* out, hipStream_t st);
 // ranked terms: each doc's 16-bit ordinal replaced by its rank (rank_of[T] as u16; 0xFFFF stays missing)
 void launch_rank_ord16(const uint16_t* ord16, uint32_t n, const uint16_t* rank_of, uint32_t T, uint16_t* out, hipStream_t st);
+// ranked terms: the 16-bit ranks saturated to a byte, min(rank, 255) (0xFFFF -> 0xFF); n a multiple of 16
+void launch_rank8(const uint16_t* rank16, uint32_t n, uint8_t* out, hipStream_t st);
 // ---- numeric ordinals (esgpu_numord.hip): a long column's sorted distinct values and each doc's rank among them ----
 // `v` with `width` 8 is the upload-width column, 4 / 2 its d32 / d16 deltas over vmin; span = vmax - vmin; the bitmap
 // holds span / 64 + 1 zeroed 64-bit words.  Spans below kNumOrdLdsBits are marked in a per-workgroup LDS bitmap.

@@ -1,5 +1,6 @@
-// esgpu_ranked.hip — the ranked-terms collect (path 10) over 16-bit rank / metric-delta columns and block-delta keys of
-// time-sorted data: a kernel of its own for the one shape that path runs at, in place of the generic collect_kernel
+// esgpu_ranked.hip — the ranked-terms collect (path 10) over the rank column (8-bit rank8, or the 16-bit rank16 it is
+// recoded from), the 16-bit metric deltas and block-delta keys of time-sorted data: a kernel of its own for the one shape
+// that path runs at, in place of the generic collect_kernel
 // (esgpu_collect.hpp), whose step loop carries multi-pass groups, the global-grid fallback, per-step prefetch scheduling
 // and the whole CollectParams block for shapes this path never sees.
 //
@@ -46,21 +47,62 @@ __device__ __forceinline__ u32x4_t rk_load16(const uint16_t* p) {
     return load16(p);
 #endif
 }
+__device__ __forceinline__ u32x2_t rk_load8(const uint8_t* p) {
+#if ESGPU_RK_NT
+    return __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(p));
+#else
+    return load8(p);
+#endif
+}
 
-// 4 docs of a single-key block: their ranks (two words of 16-bit halves) and metric deltas.  `rowm` is the LDS address of
+// The rank column at its two widths (RW bytes per doc).  rk_r4: the ranks of 4 docs as loaded -- RW 1 one word of four
+// bytes (0xFF: rank >= 255 or the missing ordinal), RW 2 two words of 16-bit halves (0xFFFF missing) -- either way a
+// rank the kernel collects (< K <= kRankedMax = 128) reads the same.  rk_r8: a thread's 8 docs of one buffer, one
+// 8-byte (RW 1) or 16-byte (RW 2) load.
+template <int RW> struct rk_r4;
+template <> struct rk_r4<1> {
+    uint32_t a;
+    __device__ __forceinline__ uint32_t at(uint32_t j) const { return (a >> (8u * j)) & 0xFFu; }
+    __device__ __forceinline__ void unpack(uint32_t (&t)[4]) const {
+        t[0] = a & 0xFFu; t[1] = (a >> 8) & 0xFFu; t[2] = (a >> 16) & 0xFFu; t[3] = a >> 24;
+    }
+};
+template <> struct rk_r4<2> {
+    uint32_t a, b;
+    __device__ __forceinline__ uint32_t at(uint32_t j) const { return ((j < 2 ? a : b) >> ((j & 1u) * 16u)) & 0xFFFFu; }
+    __device__ __forceinline__ void unpack(uint32_t (&t)[4]) const {
+        t[0] = a & 0xFFFFu; t[1] = a >> 16; t[2] = b & 0xFFFFu; t[3] = b >> 16;
+    }
+};
+template <int RW> struct rk_r8;
+template <> struct rk_r8<1> {
+    u32x2_t v;
+    __device__ __forceinline__ void load(const void* col, size_t doc) { v = rk_load8((const uint8_t*)col + doc); }
+    __device__ __forceinline__ rk_r4<1> lo() const { return {v.x}; }
+    __device__ __forceinline__ rk_r4<1> hi() const { return {v.y}; }
+};
+template <> struct rk_r8<2> {
+    u32x4_t v;
+    __device__ __forceinline__ void load(const void* col, size_t doc) { v = rk_load16((const uint16_t*)col + doc); }
+    __device__ __forceinline__ rk_r4<2> lo() const { return {v.x, v.y}; }
+    __device__ __forceinline__ rk_r4<2> hi() const { return {v.z, v.w}; }
+};
+
+// 4 docs of a single-key block: their ranks (rk_r4) and metric deltas.  `rowm` is the LDS address of
 // the block's row of (min, max) pairs, `dpk` the lane's distance from a pair to the packed word of the same cell in the
 // lane's copy, `missm` the pair of the spare cell (index K * W: never flushed, its pair (0, ~0) never moves), where the
 // docs whose rank is not collected go -- so every lane issues the same straight-line LDS traffic: 4 pair reads, then 4
 // adds, one wait for the reads; the bound atomics only where a bound moves.  MET 1 (avg): no pairs -- `rowm` / `missm`
 // then address the packed words of the lane's copy themselves and dpk is 0.
-template <int MET>
-__device__ __forceinline__ void rk_quad(uint32_t r0, uint32_t r1, uint32_t m0, uint32_t m1, uint32_t K, uint32_t rowm,
+template <int MET, int RW>
+__device__ __forceinline__ void rk_quad(rk_r4<RW> r, uint32_t m0, uint32_t m1, uint32_t K, uint32_t rowm,
                                         uint32_t missm, uint32_t dpk, uint32_t onehi) {
-    const uint32_t t[4] = {r0 & 0xFFFFu, r0 >> 16, r1 & 0xFFFFu, r1 >> 16};
+    uint32_t t[4];
+    r.unpack(t);
     const uint32_t dv[4] = {m0 & 0xFFFFu, m0 >> 16, m1 & 0xFFFFu, m1 >> 16};
     uint32_t ca[4], mlo[4], mhi[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {  // (a rank past K, the missing rank 0xFFFF included, is not collected)
+    for (int j = 0; j < 4; ++j) {  // (a rank past K, the missing rank 0xFFFF / 0xFF included, is not collected)
         ca[j] = t[j] < K ? rowm + 8u * t[j] : missm;
         if constexpr (MET >= 2) {
             const u32x2_t m = *lds_ptr<u32x2_t>(ca[j]);
@@ -82,7 +124,7 @@ __device__ __forceinline__ void rk_quad(uint32_t r0, uint32_t r1, uint32_t m0, u
     }
 }
 
-template <int MET>
+template <int MET, int RW>
 __global__ __launch_bounds__(kRkWG, ESGPU_RK_WAVES) void ranked_kernel(RankedParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t K = P.K, W = P.W, C = K * W;
@@ -164,11 +206,11 @@ __global__ __launch_bounds__(kRkWG, ESGPU_RK_WAVES) void ranked_kernel(RankedPar
         win_set = true;
     };
 
-    // any block, doc by doc: 4 docs of the thread (docs doc0 .. doc0 + 3, their rank and metric words as the block's
+    // any block, doc by doc: 4 docs of the thread (docs doc0 .. doc0 + 3, their ranks and metric words as the block's
     // buffers hold them -- the columns are not read again) with their keys by the block-delta unpack, slots by the magic
     // division of the value's distance from the block's first key (the zone map bounds the block's values, so the
     // distance is non-negative and below the block's keys x interval; a block spanning 2^32 or more divides in 64 bits)
-    auto slow_quad = [&](uint32_t doc0, uint32_t r0, uint32_t r1, uint32_t m0, uint32_t m1, int64_t kmn, int64_t kmx) {
+    auto slow_quad = [&](uint32_t doc0, rk_r4<RW> r, uint32_t m0, uint32_t m1, int64_t kmn, int64_t kmx) {
         const auto& Q = *rk_again();
         const int64_t vb = (Q.key0 + kmn) * Q.interval + Q.offset;  // the first instant of key kmn
         const bool d32 = kmx - kmn < (int64_t)Q.keys32;            // the block's keys x interval < 2^32
@@ -181,9 +223,9 @@ __global__ __launch_bounds__(kRkWG, ESGPU_RK_WAVES) void ranked_kernel(RankedPar
             const int64_t b = (int64_t)join64(bw.x, bw.y);
 #pragma unroll 1
             for (uint32_t j = 0; j < nd; ++j) {
-                const uint32_t r2 = j < 2 ? r0 : r1, m2 = j < 2 ? m0 : m1, t2 = j < 2 ? tw.x : tw.y;
+                const uint32_t m2 = j < 2 ? m0 : m1, t2 = j < 2 ? tw.x : tw.y;
                 const uint32_t hs = (j & 1u) * 16u;
-                const uint32_t t = (r2 >> hs) & 0xFFFFu, dv = (m2 >> hs) & 0xFFFFu;
+                const uint32_t t = r.at(j), dv = (m2 >> hs) & 0xFFFFu;
                 if (t >= K) continue;
                 const int64_t v = b + (int64_t)(((t2 >> hs) & 0xFFFFu) | (((hb >> (8u * j)) & 0xFFu) << 16));
                 const int64_t k = d32 ? kmn + (int64_t)magic_div((uint32_t)((uint64_t)v - (uint64_t)vb), Q.mg_m, Q.mg_s1,
@@ -224,9 +266,10 @@ __global__ __launch_bounds__(kRkWG, ESGPU_RK_WAVES) void ranked_kernel(RankedPar
     const zkey_pair_c* const zk = zkey_view(P.zkey);
     const uint32_t tid8 = threadIdx.x * kRkDocs;
     i64x2_t z = zk[__builtin_amdgcn_readfirstlane(b_begin)];
-    u32x4_t ra = rk_load16(P.rank16 + (size_t)b_begin * kBlockDocs + tid8);
+    rk_r8<RW> ra, rb;
+    ra.load(P.rank, (size_t)b_begin * kBlockDocs + tid8);
     u32x4_t ma = rk_load16(P.mv16 + (size_t)b_begin * kBlockDocs + tid8);
-    u32x4_t rb = rk_load16(P.rank16 + (size_t)b_begin * kBlockDocs + kRkStepDocs + tid8);
+    rb.load(P.rank, (size_t)b_begin * kBlockDocs + kRkStepDocs + tid8);
     u32x4_t mb = rk_load16(P.mv16 + (size_t)b_begin * kBlockDocs + kRkStepDocs + tid8);
 #pragma unroll 1
     for (uint32_t cb = b_begin; cb < b_end; ++cb) {
@@ -248,40 +291,49 @@ __global__ __launch_bounds__(kRkWG, ESGPU_RK_WAVES) void ranked_kernel(RankedPar
         const bool fast = kmn == kmx && (uint64_t)kmn < (uint64_t)P.H && (uint64_t)(cb + 1) * kBlockDocs <= P.n_docs;
         if (!fast && any) {
             const uint32_t d0 = cb * kBlockDocs + tid8;
-            slow_quad(d0, ra.x, ra.y, ma.x, ma.y, kmn, kmx);
-            slow_quad(d0 + 4u, ra.z, ra.w, ma.z, ma.w, kmn, kmx);
-            slow_quad(d0 + kRkStepDocs, rb.x, rb.y, mb.x, mb.y, kmn, kmx);
-            slow_quad(d0 + kRkStepDocs + 4u, rb.z, rb.w, mb.z, mb.w, kmn, kmx);
+            slow_quad(d0, ra.lo(), ma.x, ma.y, kmn, kmx);
+            slow_quad(d0 + 4u, ra.hi(), ma.z, ma.w, kmn, kmx);
+            slow_quad(d0 + kRkStepDocs, rb.lo(), mb.x, mb.y, kmn, kmx);
+            slow_quad(d0 + kRkStepDocs + 4u, rb.hi(), mb.z, mb.w, kmn, kmx);
         }
         dirty = dirty || any;
         // each buffer has one reload per block, outside the branches: a reload under a branch gives the buffer two
         // definitions, which the compiler joins by copying the loaded registers -- a vmcnt(0) wait per block
         const uint32_t rowm = cell0 + 8u * (((uint32_t)kmn - win0) * K);
         if (fast) {
-            rk_quad<MET>(ra.x, ra.y, ma.x, ma.y, K, rowm, missm, dpk, onehi);
-            rk_quad<MET>(ra.z, ra.w, ma.z, ma.w, K, rowm, missm, dpk, onehi);
+            rk_quad<MET, RW>(ra.lo(), ma.x, ma.y, K, rowm, missm, dpk, onehi);
+            rk_quad<MET, RW>(ra.hi(), ma.z, ma.w, K, rowm, missm, dpk, onehi);
         }
-        ra = rk_load16(P.rank16 + nd0);
+        ra.load(P.rank, nd0);
         ma = rk_load16(P.mv16 + nd0);
         if (fast) {
-            rk_quad<MET>(rb.x, rb.y, mb.x, mb.y, K, rowm, missm, dpk, onehi);
-            rk_quad<MET>(rb.z, rb.w, mb.z, mb.w, K, rowm, missm, dpk, onehi);
+            rk_quad<MET, RW>(rb.lo(), mb.x, mb.y, K, rowm, missm, dpk, onehi);
+            rk_quad<MET, RW>(rb.hi(), mb.z, mb.w, K, rowm, missm, dpk, onehi);
         }
-        rb = rk_load16(P.rank16 + nd1);
+        rb.load(P.rank, nd1);
         mb = rk_load16(P.mv16 + nd1);
     }
     if (dirty) flush();
 }
 
-void launch_ranked(const RankedParams& p, int met, uint32_t grid, size_t lds, hipStream_t st) {
-    if (met >= 2) hipLaunchKernelGGL(ranked_kernel<2>, dim3(grid), dim3(kRkWG), lds, st, p);
-    else hipLaunchKernelGGL(ranked_kernel<1>, dim3(grid), dim3(kRkWG), lds, st, p);
+// rw: the rank column's width in bytes (RankedParams.rank: 1 rank8, 2 rank16)
+template <int MET, int RW>
+static void launch_rk(const RankedParams& p, uint32_t grid, size_t lds, hipStream_t st) {
+    hipLaunchKernelGGL((ranked_kernel<MET, RW>), dim3(grid), dim3(kRkWG), lds, st, p);
+}
+void launch_ranked(const RankedParams& p, int met, int rw, uint32_t grid, size_t lds, hipStream_t st) {
+    if (met >= 2) rw == 1 ? launch_rk<2, 1>(p, grid, lds, st) : launch_rk<2, 2>(p, grid, lds, st);
+    else rw == 1 ? launch_rk<1, 1>(p, grid, lds, st) : launch_rk<1, 2>(p, grid, lds, st);
 }
 
-int ranked_occupancy(int met, size_t lds) {
+template <int MET, int RW>
+static hipError_t occ_rk(int* n, size_t lds) {
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(n, ranked_kernel<MET, RW>, kRkWG, lds);
+}
+int ranked_occupancy(int met, int rw, size_t lds) {
     int n = 0;
-    const hipError_t e = met >= 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ranked_kernel<2>, kRkWG, lds)
-                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ranked_kernel<1>, kRkWG, lds);
+    const hipError_t e = met >= 2 ? (rw == 1 ? occ_rk<2, 1>(&n, lds) : occ_rk<2, 2>(&n, lds))
+                                  : (rw == 1 ? occ_rk<1, 1>(&n, lds) : occ_rk<1, 2>(&n, lds));
     return e == hipSuccess ? n : 1;
 }
 

@@ -89,8 +89,8 @@ extern "C" int esgpu_ctx_set_option(esgpu_ctx* c, int32_t option, int64_t value)
             c->opt_num_max = value;
             return;
         }
-        if (option == ESGPU_OPT_RANKED_TERMS) {  // (2: path 10 on the generic collect kernel)
-            require(value >= 0 && value <= 2, ESGPU_ERR_INVALID, "ranked terms option must be 0..2");
+        if (option == ESGPU_OPT_RANKED_TERMS) {  // (2: path 10 on the generic collect kernel, 3: the ranked kernel over rank16)
+            require(value >= 0 && value <= 3, ESGPU_ERR_INVALID, "ranked terms option must be 0..3");
             c->opt_ranked = (int)value;
             return;
         }
@@ -316,12 +316,16 @@ struct HcStats;  // hot set + partition capacities of a high-cardinality ordinal
 // Term counts and frequency ranks of a single-valued ordinal column with fewer than 65,535 terms (ensure_term_ranks,
 // DESIGN §5 "Ranked terms"): the segment's doc count per ordinal (immutable, Lucene's docFreq), the ordinals by count
 // descending (es_term_rank.hpp) and each doc's rank in 16 bits -- the column the ranked-terms collect reads in place of
-// the 16-bit ordinals (the same 2 B per doc)
+// the 16-bit ordinals (the same 2 B per doc).  rank8 is what the ranked kernel (esgpu_ranked.hip) streams instead: the
+// rank saturated to a byte -- the kernel only asks rank < K with K <= kRankedMax = 128 -- built from rank16 the first
+// time a collect decides on that kernel (ensure_rank8: +1 B per doc of HBM, only for segments that reach it)
 struct TermRanks {
     uint32_t T = 0;
     DevBuf counts;       // u64 [T]: doc count of every ordinal
     DevBuf ord_of_rank;  // u32 [T]
     DevBuf rank16;       // u16 [n_pad]: rank of the doc's ordinal, 0xFFFF missing
+    DevBuf rank8;        // u8 [n_pad]: min(rank, 255) -- 0xFF: rank >= 255 or missing (pad docs included)
+    bool rank8_done = false;  // tried (rank8 null: being built on another thread, or over the HBM budget)
 };
 
 struct DevColumn {
@@ -1170,6 +1174,7 @@ struct esgpu_plan {
     bool collected = false, posted = false;
     double last_ms = 0;
     uint64_t last_bytes = 0;
+    uint64_t last_narrow = 0;  // bytes of last_bytes the kernel did not stream: a column read narrower than the layout counts it
     int32_t last_kernel = 0;  // the last collect's LDS-window kernel: 0 collect_kernel, 1 ranked_kernel (esgpu_ranked.hip)
     double b_wait = 0, b_total = 0;  // last build: stream waits / whole call (ms)
     bool b_trace = false;
@@ -1845,6 +1850,7 @@ static const uint16_t* ensure_ord16(esgpu_ctx* c, const DevColumn* col, const es
 static const TermRanks* ensure_term_ranks(esgpu_ctx* c, const DevColumn* col, const uint16_t* ord16, const esgpu_segment* s,
                                           hipStream_t st);
 static bool ranked_terms_on(const esgpu_ctx* c);
+static const uint8_t* ensure_rank8(esgpu_ctx* c, const TermRanks* rk, const esgpu_segment* s, hipStream_t st);
 static const DevColumn* terms_col(esgpu_plan* p, const esgpu_segment* s, const std::string& field);
 static const DevColumn* value_count_metric(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s);
 static const uint32_t* ensure_d32(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
@@ -3569,8 +3575,10 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
     // 16-bit metric deltas and block-delta keys whose typical block lies inside one key (zspan: the statistic the window
     // choice uses), in packed cells with lane-rotated copies (each copy then has a spare cell past the window's, where
     // the kernel sends the docs it does not collect).  Its per-doc body divides by the interval in 32 bits.
-    // ESGPU_OPT_RANKED_TERMS = 2 keeps path 10 on collect_kernel.
-    const bool rkk = rk && p->ctx->opt_ranked.load() == 1 && pi && P.lds_mode && L_HIST && P.hv16 && P.mv16 && !fold && !wide &&
+    // ESGPU_OPT_RANKED_TERMS = 2 keeps path 10 on collect_kernel; 3 keeps the ranked kernel on the 16-bit ranks, which 1
+    // takes only when the segment's rank8 product does not fit the HBM budget.
+    const int opt_rk = p->ctx->opt_ranked.load();
+    const bool rkk = rk && (opt_rk == 1 || opt_rk == 3) && pi && P.lds_mode && L_HIST && P.hv16 && P.mv16 && !fold && !wide &&
                      !L_vcnt && (L_met == 1 || L_met == 2) && P.ncopies > 1 && P.cstride > LK * W && !P.kstart && !P.hord && hc &&
                      pl.interval > 0 && pl.interval < (1ll << 32) && hc->zspan < pl.interval && !dyn_claim_on();
     const int vk = (P.hv_f64 ? 1 : 0) | (P.mv_f64 ? 2 : 0) | (P.ord_src ? 8 : 0) | (P.ord16 ? 16 : 0) | (P.hv32 ? 32 : 0) |
@@ -3578,9 +3586,9 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
                    (P.runs1 ? 4096 : 0) | (P.hv16 ? 8192 : 0) | (P.ukey32 ? 16384 : 0) |
                    (P.ocnt_mode != OCNT_TERMS && P.ocnt_mode != OCNT_HIST ? 32768 : 0) | (P.rank_cells ? 65536 : 0);
     const uint64_t occ_key = ((uint64_t)lds << 24) | ((uint64_t)wide << 23) | ((uint64_t)vk << 8) | ((uint64_t)L_met << 4) |
-                             ((uint64_t)hk << 1) | (L_ORD ? 1 : 0) | (rkk ? 1ull << 63 : 0);
+                             ((uint64_t)hk << 1) | (L_ORD ? 1 : 0) | (rkk ? (opt_rk == 1 ? 3ull : 2ull) << 62 : 0);
     if (pl.occ_key != occ_key) {
-        pl.occ = std::max(1, rkk ? ranked_occupancy(L_met, lds) : collect_occupancy(L_ORD, hk, L_met, lds, vk, wide));
+        pl.occ = std::max(1, rkk ? ranked_occupancy(L_met, opt_rk == 1 ? 1 : 2, lds) : collect_occupancy(L_ORD, hk, L_met, lds, vk, wide));
         pl.occ_key = occ_key;
     }
     const uint32_t wg_per_cu = (uint32_t)pl.occ;
@@ -3665,6 +3673,10 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
         }
     }
     need_wide(false);
+    // the ranked kernel's 8-bit ranks, built here on first use (outside the timed region, like the other products); over
+    // the HBM budget, or while another thread builds them, this request streams the 16-bit ranks
+    const uint8_t* r8 = rkk && opt_rk == 1 ? ensure_rank8(p->ctx, rk, s, p->stream) : nullptr;
+    const int rk_width = r8 ? 1 : 2;
     HIPX(hipEventRecord(pl.e0, p->stream));
     if (fold && P.npred > 0) {  // (inside the timed region: part of the collect)
         uint64_t* bits = (uint64_t*)p->s_xbits.ensure(p->ctx, std::max<size_t>(s->n_pad / 64, 1) * 8);
@@ -3678,7 +3690,7 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
     if (rkk) {
         require(!P.claim && P.zkey, ESGPU_ERR_DEVICE, "internal: ranked kernel without static ranges or zone keys");
         RankedParams R{};
-        R.rank16 = P.ord16;
+        R.rank = r8 ? (const void*)r8 : (const void*)P.ord16;
         R.mv16 = P.mv16;
         R.hv16 = P.hv16;
         R.hv16_base = P.hv16_base;
@@ -3709,7 +3721,7 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
         R.n_docs = P.n_docs;
         R.n_blocks = P.n_blocks;
         R.blocks_per_wg = P.blocks_per_wg;
-        launch_ranked(R, L_met, grid, lds, p->stream);
+        launch_ranked(R, L_met, rk_width, grid, lds, p->stream);
     } else {
         launch_collect(P, L_ORD, L_HIST, L_met, wide, grid, lds, p->stream);
     }
@@ -3717,6 +3729,7 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
     HIPX(hipEventRecord(pl.e1, p->stream));
     dd_fold();
     p->last_kernel = rkk ? 1 : 0;
+    if (rkk && rk_width == 1) p->last_narrow += s->max_doc;  // (last_bytes counts the rank at the ordinals' 2 bytes)
     p->last_bytes += bytes_per_doc * (uint64_t)s->max_doc + (d_accept ? ((uint64_t)s->max_doc + 7) / 8 : 0) +
                      (P.hv16 ? (((uint64_t)s->max_doc + kB16Docs - 1) >> kB16Shift) * 8 : 0);
     p->last_path = rk ? 10 : P.lds_mode ? (P.windowed ? 2 : 1) : 0;
@@ -3873,6 +3886,31 @@ static const TermRanks* ensure_term_ranks(esgpu_ctx* c, const DevColumn* col, co
     std::lock_guard<std::mutex> lk(c->mu);
     m->ranks = std::move(r);
     return m->ranks.get();
+}
+// the 8-bit rank column of the ranked kernel, built from rank16 on the first collect that launches that kernel on the
+// segment and kept with the ranks (charged to the HBM budget; over the budget: null, and the kernel streams rank16)
+static const uint8_t* ensure_rank8(esgpu_ctx* c, const TermRanks* rk, const esgpu_segment* s, hipStream_t st) {
+    TermRanks* m = const_cast<TermRanks*>(rk);
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        if (m->rank8_done) return m->rank8.as<uint8_t>();
+        m->rank8_done = true;
+    }
+    // (built outside the lock, published under it once the recode has finished: a plan on another thread that asks
+    // meanwhile streams rank16 this once)
+    DevBuf b;
+    try {
+        b.alloc(c, (size_t)s->n_pad);
+        launch_rank8(rk->rank16.as<uint16_t>(), s->n_pad, b.as<uint8_t>(), st);
+        HIPX(hipGetLastError());
+        HIPX(hipStreamSynchronize(st));
+    } catch (const EsError& e) {
+        if (e.code != ESGPU_ERR_OOM) throw;
+        return nullptr;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    m->rank8 = std::move(b);
+    return m->rank8.as<uint8_t>();
 }
 
 // the 4 most frequent ordinals among 64 evenly spaced runs of 4,096 docs, most frequent first (cached with the ordinal
@@ -4451,6 +4489,7 @@ extern "C" int esgpu_plan_collect_segment(esgpu_plan* p, const esgpu_segment* s,
             collect_grid(p, pl, p->dsegs[0].s, nullptr);
         }
         p->last_bytes = 0;
+        p->last_narrow = 0;
         p->last_ms = -1;
         p->last_kernel = 0;
         p->zu_n = 0;
@@ -4504,39 +4543,53 @@ extern "C" int esgpu_plan_deferred_segments(const esgpu_plan* p, int32_t* n) {
     });
 }
 
+// resolve the last collect's kernel time and bytes (synchronises with it)
+static void resolve_collect_stats(esgpu_plan* p) {
+    if (p->last_ms < 0) {  // resolve the HIP events of the last collect (synchronises with it)
+        float total = 0;
+        for (Pipeline& pl : p->pipes) {
+            if (!pl.timed) continue;
+            HIPX(hipEventSynchronize(pl.e1));
+            float ms = 0;
+            HIPX(hipEventElapsedTime(&ms, pl.e0, pl.e1));
+            total += ms;
+        }
+        p->last_ms = total;
+        if (p->zu_n) {  // the timestamps of single-key zone blocks were not read
+            p->zu_host.ensure((size_t)kZuSlots * kZuMaxWG * 8);
+            for (uint32_t i = 0; i < p->zu_n; ++i)
+                launch_copy_u64(p->s_zu.as<unsigned long long>() + (size_t)i * kZuMaxWG,
+                                (unsigned long long*)p->zu_host.dev() + (size_t)i * kZuMaxWG, p->zu_g[i], p->stream);
+            HIPX(hipGetLastError());
+            HIPX(hipStreamSynchronize(p->stream));
+            uint64_t ud = 0;
+            for (uint32_t i = 0; i < p->zu_n; ++i) {
+                uint64_t w = 0;
+                for (uint32_t g = 0; g < p->zu_g[i]; ++g) w += ((const uint64_t*)p->zu_host.p)[(size_t)i * kZuMaxWG + g];
+                ud += w * p->zu_w[i];
+            }
+            p->last_bytes -= std::min<uint64_t>(p->last_bytes, ud);
+            p->zu_n = 0;
+        }
+    }
+}
+
 extern "C" int esgpu_plan_last_collect_stats(const esgpu_plan* cp, double* kernel_ms, uint64_t* bytes, int32_t* path) {
     return guarded([&] {
         esgpu_plan* p = const_cast<esgpu_plan*>(cp);
-        if (p->last_ms < 0) {  // resolve the HIP events of the last collect (synchronises with it)
-            float total = 0;
-            for (Pipeline& pl : p->pipes) {
-                if (!pl.timed) continue;
-                HIPX(hipEventSynchronize(pl.e1));
-                float ms = 0;
-                HIPX(hipEventElapsedTime(&ms, pl.e0, pl.e1));
-                total += ms;
-            }
-            p->last_ms = total;
-            if (p->zu_n) {  // the timestamps of single-key zone blocks were not read
-                p->zu_host.ensure((size_t)kZuSlots * kZuMaxWG * 8);
-                for (uint32_t i = 0; i < p->zu_n; ++i)
-                    launch_copy_u64(p->s_zu.as<unsigned long long>() + (size_t)i * kZuMaxWG,
-                                    (unsigned long long*)p->zu_host.dev() + (size_t)i * kZuMaxWG, p->zu_g[i], p->stream);
-                HIPX(hipGetLastError());
-                HIPX(hipStreamSynchronize(p->stream));
-                uint64_t ud = 0;
-                for (uint32_t i = 0; i < p->zu_n; ++i) {
-                    uint64_t w = 0;
-                    for (uint32_t g = 0; g < p->zu_g[i]; ++g) w += ((const uint64_t*)p->zu_host.p)[(size_t)i * kZuMaxWG + g];
-                    ud += w * p->zu_w[i];
-                }
-                p->last_bytes -= std::min<uint64_t>(p->last_bytes, ud);
-                p->zu_n = 0;
-            }
-        }
+        resolve_collect_stats(p);
         if (kernel_ms) *kernel_ms = p->last_ms;
         if (bytes) *bytes = p->last_bytes;
         if (path) *path = p->last_path;
+    });
+}
+
+extern "C" int esgpu_plan_last_collect_read_bytes(const esgpu_plan* cp, uint64_t* bytes) {
+    return guarded([&] {
+        require(cp != nullptr && bytes != nullptr, ESGPU_ERR_INVALID, "null argument");
+        esgpu_plan* p = const_cast<esgpu_plan*>(cp);
+        resolve_collect_stats(p);
+        *bytes = p->last_bytes - std::min(p->last_bytes, p->last_narrow);
     });
 }
 

@@ -236,6 +236,12 @@ class Plan:
         N.check(N.lib().esgpu_plan_last_collect_kernel(self._ptr, ctypes.byref(kid)))
         return kid.value
 
+    def last_collect_read_bytes(self):
+        """the bytes the last collect's kernels streamed at the widths they read (last_collect_stats()[1] is the layout's)"""
+        nbytes = ctypes.c_uint64()
+        N.check(N.lib().esgpu_plan_last_collect_read_bytes(self._ptr, ctypes.byref(nbytes)))
+        return nbytes.value
+
     def last_build_stats(self):
         """(total_ms, stream_wait_ms) of the last build()"""
         tot, wait = ctypes.c_double(), ctypes.c_double()
@@ -290,7 +296,8 @@ class Engine:
 
     def set_option(self, name, value):
         """Layout option of this context (esgpu_ctx_set_option): 'compact_columns' / 'packed_metric' / 'block_deltas' /
-        0 or 1; 'ranked_terms' 0, 1 or 2 (2: path 10 on the generic collect kernel instead of the ranked kernel);
+        0 or 1; 'ranked_terms' 0..3 (2: path 10 on the generic collect kernel instead of the ranked kernel, 3: the ranked kernel
+        over the 16-bit ranks instead of the 8-bit ones);
         'hll_floor' 0..8 (include/esgpu.h ESGPU_OPT_HLL_FLOOR); 'numeric_terms_max_distinct': the distinct values of a long field
         in one segment above which terms over it are refused (default 2^22)."""
         N.check(N.lib().esgpu_ctx_set_option(self._ptr, self.OPTIONS[name], int(value)))

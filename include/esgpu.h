@@ -89,6 +89,9 @@ int esgpu_device_count(int* count);
  *                              pass cached per segment).  0 collects every term; 1 (the default) runs the
  *                              collect on the ranked kernel where the shape allows (stats / avg over 16-bit metric
  *                              deltas, block-delta keys of time-sorted data), 2 always on the generic collect kernel.
+ *                              The ranked kernel streams each doc's frequency rank as one byte (the segment's rank8
+ *                              product: min(rank, 255), built on the first such collect, +1 B per doc of HBM; over the
+ *                              HBM budget it streams the 16-bit ranks instead); 3 keeps it on the 16-bit ranks.
  *                              Not read from the environment.
  * and one limit:
  *   ESGPU_OPT_NUMERIC_TERMS_MAX_DISTINCT: terms over a long / date field count by the segment's numeric ordinals; a
@@ -403,7 +406,9 @@ int esgpu_plan_build(esgpu_plan* plan, esgpu_result** out);
 int esgpu_plan_reset(esgpu_plan* plan);
 int esgpu_plan_destroy(esgpu_plan* plan);
 /* Timing of the last collect_segment's dominant kernel (HIP events on the plan's stream), in milliseconds,
- * and the algorithmic bytes it read (SURVEY §8(d) formula).  path: the collect form -- 0 grid in global memory,
+ * and the algorithmic bytes it read (SURVEY §8(d) formula): the layout's bytes -- every column at the width of the
+ * layout's copy of it, a ranked collect's rank column at the 2 bytes of the ordinals it stands in for, whatever width
+ * the kernel streamed (esgpu_plan_last_collect_read_bytes gives that).  path: the collect form -- 0 grid in global memory,
  * 1 LDS grid, 2 LDS key window, 3 HLL registers, 4 partitioned terms counting, 5 multi-valued (CSR) columns, 6 hot/cold
  * terms scatter form, 7 hot/cold postings form, 8 hot slots only (cold lists deferred to the top-k), 9 hot slots of a
  * filtered request (the scatter form deferred to the top-k), 10 LDS key window over the top-ranked terms (the segment
@@ -413,6 +418,9 @@ int esgpu_plan_last_collect_stats(const esgpu_plan* plan, double* kernel_ms, uin
 /* The kernel that ran the last collect's LDS-window launch: 0 the generic collect kernel, 1 the ranked kernel (path 10
  * where ESGPU_OPT_RANKED_TERMS = 1 and the shape allows). */
 int esgpu_plan_last_collect_kernel(const esgpu_plan* plan, int32_t* id);
+/* The bytes the last collect's kernels streamed, at the widths they read: esgpu_plan_last_collect_stats' figure, less
+ * one byte per doc where the ranked kernel ran over the 8-bit ranks.  Equal to that figure on every other path. */
+int esgpu_plan_last_collect_read_bytes(const esgpu_plan* plan, uint64_t* bytes);
 /* Wall time of the last esgpu_plan_build and the part of it spent waiting on the plan's stream (gathers and copies of
  * the winners' cells); the rest is host assembly of the result blocks.  Milliseconds. */
 int esgpu_plan_last_build_stats(const esgpu_plan* plan, double* total_ms, double* wait_ms);

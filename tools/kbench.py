@@ -170,6 +170,10 @@ def main():
         ea.reduce([res])
         t5 = time.perf_counter()
         run["bytes"], run["path"] = nbytes, path
+        try:
+            run["read_bytes"] = plan.last_collect_read_bytes()
+        except AttributeError:  # an older variant build (ESGPU_LIBRARY): every column at the layout's width
+            run["read_bytes"] = nbytes
         if r:  # first is warmup
             run["ms"].append(k)
             run["steps"].append((t5 - t0) * 1e3)
@@ -185,6 +189,8 @@ def main():
         gbs = nbytes / (kms / 1e3) / 1e9
         line = {"name": name, "ts_jitter_ms": args.ts_jitter, "deletes": args.deletes, "kernel_ms": round(kms, 4), "bytes": nbytes,
                 "gbs": round(gbs, 1), "frac": round(gbs / 8000, 4), "path": run["path"],
+                # what the kernel streamed at the widths it read ("bytes" is the layout's figure), and the physical rate
+                "read_bytes": run["read_bytes"], "read_gbs": round(run["read_bytes"] / (kms / 1e3) / 1e9, 1),
                 "step_ms": round(sorted(steps)[len(steps) // 2], 3), "docs_per_s": args.docs / (kms / 1e3),
                 "parts_ms": {k: round(sorted(v)[len(v) // 2], 3) for k, v in run["parts"].items()}}
         if args.alternate:
