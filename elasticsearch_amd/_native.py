@@ -25,7 +25,7 @@ SYNTH_TYPES = {
     "response_time_ms": COL_I64, "bytes": COL_I64, "client_ip.hash": COL_U64, "price": COL_F64,
 }
 AGG_TERMS, AGG_HISTOGRAM, AGG_DATE_HISTOGRAM, AGG_STATS, AGG_EXTENDED_STATS, AGG_AVG, AGG_CARDINALITY = 1, 2, 3, 4, 5, 6, 7
-AGG_SUM, AGG_MIN, AGG_MAX, AGG_VALUE_COUNT, AGG_FILTER = 8, 9, 10, 11, 12
+AGG_SUM, AGG_MIN, AGG_MAX, AGG_VALUE_COUNT, AGG_FILTER, AGG_RANGE = 8, 9, 10, 11, 12, 13
 ORDER_COUNT_DESC, ORDER_COUNT_ASC, ORDER_TERM_ASC, ORDER_TERM_DESC = 0, 1, 2, 3
 ORDER_KEY_ASC, ORDER_KEY_DESC, ORDER_HCOUNT_ASC, ORDER_HCOUNT_DESC = 4, 5, 6, 7
 ORDER_AGG_ASC, ORDER_AGG_DESC = 8, 9
@@ -45,6 +45,11 @@ class ColumnDesc(ctypes.Structure):
     ]
 
 
+class Range(ctypes.Structure):
+    """esgpu_range: one [from, to) of a range aggregation; key None = the generated key, +-inf = an unbounded side"""
+    _fields_ = [("key", ctypes.c_char_p), ("from_", ctypes.c_double), ("to", ctypes.c_double)]
+
+
 class AggSpec(ctypes.Structure):
     _fields_ = [
         ("type", ctypes.c_int32), ("parent", ctypes.c_int32), ("name", ctypes.c_char_p), ("field", ctypes.c_char_p),
@@ -58,6 +63,7 @@ class AggSpec(ctypes.Structure):
         ("tz_count", ctypes.c_int32), ("reserved_tz", ctypes.c_int32), ("order_path", ctypes.c_char_p),
         ("time_zone", ctypes.c_char_p), ("value_format", ctypes.c_int32), ("reserved_fmt", ctypes.c_int32),
         ("format", ctypes.c_char_p),
+        ("ranges", ctypes.POINTER(Range)), ("n_ranges", ctypes.c_int32), ("reserved_ranges", ctypes.c_int32),
     ]
 
 
@@ -98,6 +104,7 @@ AggBlock._fields_ = [
     ("order_path", ctypes.c_char_p),
     ("time_zone", ctypes.c_char_p), ("value_format", _I32), ("reserved_fmt", _I32), ("format", ctypes.c_char_p),
     ("terms_kind", _I32), ("reserved_kind", _I32), ("term_longs", ctypes.POINTER(_I64)),  # 1 = LongTerms
+    ("range_from", ctypes.POINTER(_F64)), ("range_to", ctypes.POINTER(_F64)),  # range: the buckets' bounds
 ]
 
 
@@ -149,6 +156,8 @@ SIGNATURES = [
     ("esgpu_precision_from_threshold", ctypes.c_int, [ctypes.c_int64, ctypes.POINTER(ctypes.c_int32)]),
     ("esgpu_date_rounding", ctypes.c_int, [ctypes.POINTER(AggSpec), ctypes.c_int32, ctypes.c_int64,
                                            ctypes.POINTER(ctypes.c_int64)]),
+    ("esgpu_range_buckets", ctypes.c_int, [ctypes.POINTER(AggSpec), ctypes.POINTER(ctypes.c_int32), ctypes.c_char_p,
+                                           ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     ("esgpu_routing_hash", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)]),
     ("esgpu_route_shards", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_uint64, ctypes.c_int32, _VP, _VP]),
     ("esgpu_murmur3_field", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_uint64, _VP]),

@@ -341,9 +341,52 @@ class FilterBuilder(_Builder):
         return list(q) if isinstance(q, (list, tuple)) else [q]
 
 
+class RangeBuilder(_Builder):
+    """range aggregation (RangeAggregator / InternalRange): one bucket per [from, to) over a long, date or double field,
+    every range emitted, sorted by (from, to).  On the GPU path at the top level with numeric metric sub-aggregations."""
+    type = N.AGG_RANGE
+
+    def __init__(self, name):
+        super().__init__(name)
+        self._ranges = []  # (key or None, from, to) in request order
+        self._keyed = False
+
+    @staticmethod
+    def _key_and(args, n):
+        if len(args) == n + 1:
+            return (args[0],) + tuple(float(a) for a in args[1:])
+        if len(args) != n:
+            raise TypeError("expected [key,] and %d bound(s)" % n)
+        return (None,) + tuple(float(a) for a in args)
+
+    def addRange(self, *args):  # noqa: N802 -- addRange([key,] from, to)
+        key, lo, hi = self._key_and(args, 2)
+        self._ranges.append((key, lo, hi))
+        return self
+
+    def addUnboundedTo(self, *args):  # noqa: N802 -- addUnboundedTo([key,] to): (-inf, to)
+        key, hi = self._key_and(args, 1)
+        self._ranges.append((key, float("-inf"), hi))
+        return self
+
+    def addUnboundedFrom(self, *args):  # noqa: N802 -- addUnboundedFrom([key,] from): [from, +inf)
+        key, lo = self._key_and(args, 1)
+        self._ranges.append((key, lo, float("inf")))
+        return self
+
+    def keyed(self, k):
+        self._keyed = bool(k)
+        return self
+
+    add_range = addRange
+    add_unbounded_to = addUnboundedTo
+    add_unbounded_from = addUnboundedFrom
+
+
 class AggregationBuilders:
     terms = TermsBuilder
     filter = FilterBuilder
+    range = RangeBuilder
     histogram = HistogramBuilder
     dateHistogram = DateHistogramBuilder
     date_histogram = DateHistogramBuilder
@@ -528,6 +571,14 @@ def flatten(aggs, number_of_shards=1):
             if hi is not None:
                 sp.has_extended_bounds_max = 1
                 sp.extended_bounds_max = _round_bound(sp, hi)
+        elif b.type == N.AGG_RANGE:
+            sp.keyed = int(b._keyed)
+            rs = (N.Range * max(len(b._ranges), 1))()
+            for k, (key, lo, hi) in enumerate(b._ranges):
+                rs[k].key, rs[k].from_, rs[k].to = enc(key), lo, hi
+            keep.append(rs)
+            sp.ranges = ctypes.cast(rs, ctypes.POINTER(N.Range))
+            sp.n_ranges = len(b._ranges)
         elif b.type == N.AGG_EXTENDED_STATS:
             sp.sigma = b._sigma
         elif b.type == N.AGG_CARDINALITY:

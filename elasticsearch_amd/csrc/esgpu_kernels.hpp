@@ -185,6 +185,36 @@ struct RankedParams {
     uint32_t n_docs, n_blocks, blocks_per_wg;
 };
 
+// The range collect (esgpu_range.hip, path 11): one pass over the range field and one metric field into the [R] cells
+// of a pipeline's ordinary grid (T = R ranges, H = 1).  The ranges reach the kernel as a table over the elementary
+// intervals their distinct finite bounds cut the number line into: `cuts` ascending (doubles for an F64 field; for an I64
+// field the least long whose double is >= the bound, so that the long comparison equals the reference's comparison of
+// (double) value), and for interval k -- the values with exactly k cuts <= value -- the u64 mask of the ranges holding it.
+constexpr uint32_t kRangeMax = 64;                   // ranges per aggregation (one mask word per doc)
+constexpr uint32_t kRangeCuts = 2 * kRangeMax;       // distinct finite bounds at most
+struct RangeParams {
+    const void* rv;              // the range field's values: 8 bytes each, per doc or (rv_off) per CSR value
+    const uint64_t* rv_present;  // null = dense (single-valued fields only)
+    const uint64_t* rv_off;      // multi-valued: CSR offsets [n_docs + 1]
+    const void* mv;              // the metric field's values, single-valued, 8 bytes per doc (null: counts only)
+    const uint64_t* mv_present;
+    const uint64_t* accept;      // doc bitset: accept bits and every clause folded (launch_filter_bits); null = all docs
+    const uint64_t* table;       // device: [kRangeCuts] cuts, then [kRangeCuts + 1] masks
+    uint32_t n_cuts, R;
+    int32_t rv_f64, mv_f64, vcnt_mode;
+    uint32_t n_docs, n_blocks, blocks_per_wg;
+    unsigned long long* g_cnt;
+    unsigned long long* g_vcnt;
+    double* g_sum;
+    unsigned long long* g_min;
+    unsigned long long* g_max;
+    double* g_sq;
+    double* g_sum_lo;
+    double* g_sq_lo;
+};
+void launch_range(const RangeParams& p, int met, uint32_t grid, hipStream_t s);
+int range_occupancy(int met, bool multi);
+
 enum HllKind : int32_t { HLL_I64 = 0, HLL_F64 = 1, HLL_ORD = 2 };
 
 struct HllParams {

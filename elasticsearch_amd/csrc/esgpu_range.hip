@@ -1,0 +1,241 @@
+// esgpu_range.hip — the range aggregation's collect (path 11, RangeAggregator.java:128-190): one pass over the range
+// field and one metric field into the [R] cells of a pipeline's ordinary grid.
+//
+// A doc may fall into several ranges, so the bucket dimension is a u64 mask per doc instead of a cell index.  The host
+// cuts the number line at the ranges' distinct finite bounds (RangeParams): a value's mask is the table entry of its
+// elementary interval, found by a binary search over the cuts in LDS -- no loop over the ranges per value -- and a doc's
+// mask is the OR over its values (a multi-valued doc counts once per range).  Values are compared as signed 64-bit keys:
+// a long column against long cuts (the host made each the least long whose double reaches the bound), a double column
+// through the order-preserving image of its bits (rg_key; NaN and +Infinity belong to no range).
+//
+// Accumulation: a thread holds 8 docs (masks and metric values) in registers; for every range present in the wave the
+// wave reduces first -- ballots for the counts, wave_sum_f64 / wave_min_u64 / wave_max_u64 for the metric -- and lane 0
+// updates the workgroup's LDS cell of that range once.  The cells reach the grid in one flush per workgroup, one atomic
+// per non-empty cell and array (compensated where the pipeline's double-double rule is on).  No global atomic and no
+// LDS atomic per doc.
+#include "esgpu_collect.hpp"
+
+namespace esgpu {
+
+constexpr int kRgWG = 256;
+constexpr uint32_t kRgQuad = kRgWG * 4;        // docs of one 16-byte-per-lane sweep of the workgroup (two loads per column)
+constexpr uint32_t kRgQuads = 2;               // sweeps per reduction round
+constexpr uint32_t kRgDocs = 4 * kRgQuads;     // docs per thread per round
+constexpr uint32_t kRgRound = kRgQuad * kRgQuads;
+static_assert(kBlockDocs % kRgRound == 0, "a zone block is a whole number of rounds");
+
+struct RgLds {
+    long long cuts[kRangeCuts];
+    unsigned long long masks[kRangeCuts + 1];
+    unsigned long long cnt[kRangeMax], vcnt[kRangeMax];
+    double sum[kRangeMax];
+    unsigned long long mn[kRangeMax], mx[kRangeMax];
+    double sq[kRangeMax];
+};
+
+// the signed key doubles compare by (-0.0 just below +0.0: the host's cut for a bound of 0.0 is the key of -0.0)
+__device__ __forceinline__ long long rg_key(unsigned long long bits) {
+    const long long b = (long long)bits;
+    return b ^ ((b >> 63) & 0x7FFFFFFFFFFFFFFFll);
+}
+
+// mask of a value: masks[k], k = the number of cuts <= key (the largest k in [0, n] with cuts[k - 1] <= key)
+__device__ __forceinline__ unsigned long long rg_lookup(const RgLds& S, uint32_t n, uint32_t step0, long long key) {
+    uint32_t k = 0;
+    for (uint32_t step = step0; step; step >>= 1) {
+        const uint32_t t = k + step;
+        if (t <= n && S.cuts[t - 1] <= key) k = t;
+    }
+    return S.masks[k];
+}
+template <bool F64>
+__device__ __forceinline__ unsigned long long rg_value_mask(const RgLds& S, uint32_t n, uint32_t step0, unsigned long long bits) {
+    if (F64) {
+        const double d = bits_dbl(bits);
+        if (!(d < INFINITY)) return 0ull;  // NaN >= from and +Infinity < to are false for every range
+        return rg_lookup(S, n, step0, rg_key(bits));
+    }
+    return rg_lookup(S, n, step0, (long long)bits);
+}
+
+__device__ __forceinline__ unsigned long long wave_or_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <int MET, bool MULTI>
+__global__ __launch_bounds__(kRgWG) void range_kernel(RangeParams P) {
+    __shared__ RgLds S;
+    const uint32_t n = P.n_cuts, R = P.R;
+    for (uint32_t i = threadIdx.x; i < n; i += kRgWG) S.cuts[i] = (long long)P.table[i];
+    for (uint32_t i = threadIdx.x; i <= n; i += kRgWG) S.masks[i] = P.table[kRangeCuts + i];
+    for (uint32_t i = threadIdx.x; i < kRangeMax; i += kRgWG) {
+        S.cnt[i] = 0;
+        S.vcnt[i] = 0;
+        S.sum[i] = 0.0;
+        S.mn[i] = kMinInit;
+        S.mx[i] = kMaxInit;
+        S.sq[i] = 0.0;
+    }
+    __syncthreads();
+    uint32_t step0 = 0;
+    if (n) step0 = 1u << (31 - __clz((int)n));
+
+    const uint32_t b_begin = blockIdx.x * P.blocks_per_wg;
+    const uint32_t b_end = min(b_begin + P.blocks_per_wg, P.n_blocks);
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    const bool vcnt = MET > 0 && P.vcnt_mode != 0;
+
+    for (uint32_t base = b_begin * kBlockDocs; base < b_end * kBlockDocs; base += kRgRound) {
+        if (base >= P.n_docs) break;  // (uniform: the rest of the last block is padding)
+        unsigned long long m[kRgDocs];
+        double x[kRgDocs];
+        uint32_t mp = 0;  // bit j: doc j has a metric value
+        if constexpr (!MULTI) {
+            // single-valued range field: 4 consecutive docs per quad, every column by 16-byte loads (the columns, present
+            // bitsets and the doc bitset are allocated over whole zone blocks; what lies past n_docs is masked below)
+            long long rv[kRgDocs], mvv[kRgDocs];
+            uint32_t ok = 0;
+#pragma unroll
+            for (uint32_t q = 0; q < kRgQuads; ++q) {
+                const uint32_t doc0 = base + q * kRgQuad + threadIdx.x * 4;
+                load_i64x4((const int64_t*)P.rv, doc0, (int64_t*)&rv[4 * q]);
+                if constexpr (MET > 0) load_i64x4((const int64_t*)P.mv, doc0, (int64_t*)&mvv[4 * q]);
+                uint32_t o = 0xFu;
+                if (P.accept) o &= bits4(P.accept, doc0);
+                if (P.rv_present) o &= bits4(P.rv_present, doc0);
+                const uint32_t left = doc0 < P.n_docs ? P.n_docs - doc0 : 0u;
+                if (left < 4) o &= (1u << left) - 1u;
+                ok |= o << (4 * q);
+                if constexpr (MET > 0) mp |= (P.mv_present ? bits4(P.mv_present, doc0) : 0xFu) << (4 * q);
+            }
+#pragma unroll
+            for (uint32_t j = 0; j < kRgDocs; ++j) {
+                const unsigned long long vm = P.rv_f64 ? rg_value_mask<true>(S, n, step0, (unsigned long long)rv[j])
+                                                       : rg_value_mask<false>(S, n, step0, (unsigned long long)rv[j]);
+                m[j] = ((ok >> j) & 1u) ? vm : 0ull;
+                if constexpr (MET > 0) x[j] = P.mv_f64 ? bits_dbl((unsigned long long)mvv[j]) : (double)mvv[j];
+            }
+        } else {
+            // multi-valued range field (CSR): one doc per lane and sweep, its values in a loop
+#pragma unroll
+            for (uint32_t j = 0; j < kRgDocs; ++j) {
+                const uint32_t d = base + j * kRgWG + threadIdx.x;
+                m[j] = 0ull;
+                if constexpr (MET > 0) x[j] = 0.0;
+                if (d >= P.n_docs) continue;
+                if (P.accept && !((P.accept[d >> 6] >> (d & 63)) & 1ull)) continue;
+                const unsigned long long* vals = (const unsigned long long*)P.rv;
+                const uint64_t o1 = P.rv_off[d + 1];
+                unsigned long long acc = 0ull;
+                for (uint64_t o = P.rv_off[d]; o < o1; ++o)
+                    acc |= P.rv_f64 ? rg_value_mask<true>(S, n, step0, vals[o]) : rg_value_mask<false>(S, n, step0, vals[o]);
+                m[j] = acc;
+                if constexpr (MET > 0) {
+                    const long long raw = ((const long long*)P.mv)[d];
+                    x[j] = P.mv_f64 ? bits_dbl((unsigned long long)raw) : (double)raw;
+                    if (!P.mv_present || ((P.mv_present[d >> 6] >> (d & 63)) & 1ull)) mp |= 1u << j;
+                }
+            }
+        }
+        unsigned long long any = 0ull;
+#pragma unroll
+        for (uint32_t j = 0; j < kRgDocs; ++j) any |= m[j];
+        any = wave_or_u64(any);
+        uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)any), hi = __builtin_amdgcn_readfirstlane((uint32_t)(any >> 32));
+        // one pass per range present in the wave (uniform)
+        while (lo | hi) {
+            uint32_t r;
+            if (lo) { r = __builtin_ctz(lo); lo &= lo - 1u; }
+            else { r = 32u + __builtin_ctz(hi); hi &= hi - 1u; }
+            uint32_t c = 0, vc = 0;
+            double s = 0.0, sq = 0.0;
+            unsigned long long mn = kMinInit, mx = kMaxInit;
+#pragma unroll
+            for (uint32_t j = 0; j < kRgDocs; ++j) {
+                const bool in = (m[j] >> r) & 1ull;
+                c += __popcll(__ballot(in));
+                if constexpr (MET > 0) {
+                    const bool has = in && ((mp >> j) & 1u);
+                    if (vcnt) vc += __popcll(__ballot(has));
+                    s += has ? x[j] : 0.0;
+                    if constexpr (MET >= 2) {
+                        const bool nan = x[j] != x[j];
+                        const unsigned long long e = sortable(x[j]);
+                        const unsigned long long emn = nan ? 0ull : e, emx = nan ? ~0ull : e;
+                        if (has && emn < mn) mn = emn;
+                        if (has && emx > mx) mx = emx;
+                    }
+                    if constexpr (MET >= 3) sq += has ? x[j] * x[j] : 0.0;  // (sumOfSqr += value * value, no FMA)
+                }
+            }
+            if constexpr (MET > 0) {
+                s = wave_sum_f64(s);
+                if constexpr (MET >= 2) {
+                    mn = wave_min_u64(mn);
+                    mx = wave_max_u64(mx);
+                }
+                if constexpr (MET >= 3) sq = wave_sum_f64(sq);
+            }
+            if (lane0) {
+                atomicAdd(&S.cnt[r], (unsigned long long)c);
+                if constexpr (MET > 0) {
+                    if (vcnt) atomicAdd(&S.vcnt[r], (unsigned long long)vc);
+                    atomicAdd(&S.sum[r], s);
+                    if constexpr (MET >= 2) {
+                        atomicMin(&S.mn[r], mn);
+                        atomicMax(&S.mx[r], mx);
+                    }
+                    if constexpr (MET >= 3) atomicAdd(&S.sq[r], sq);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // the workgroup's cells into the grid: one atomic per non-empty cell and array
+    const uint32_t r = threadIdx.x;
+    if (r < R && S.cnt[r] != 0) {
+        atomicAdd(&P.g_cnt[r], S.cnt[r]);
+        if constexpr (MET > 0) {
+            const bool some = !vcnt || S.vcnt[r] != 0;  // (docs of the range, none with a metric value: nothing to add)
+            if (vcnt && some) atomicAdd(&P.g_vcnt[r], S.vcnt[r]);
+            if (some) {
+                dd_atomic_add(&P.g_sum[r], P.g_sum_lo ? P.g_sum_lo + r : nullptr, S.sum[r]);
+                if constexpr (MET >= 2) {
+                    if (S.mn[r] != kMinInit) atomicMin(&P.g_min[r], S.mn[r]);
+                    if (S.mx[r] != kMaxInit) atomicMax(&P.g_max[r], S.mx[r]);
+                }
+                if constexpr (MET >= 3) dd_atomic_add(&P.g_sq[r], P.g_sq_lo ? P.g_sq_lo + r : nullptr, S.sq[r]);
+            }
+        }
+    }
+}
+
+template <int MET>
+static void launch_rg(const RangeParams& p, uint32_t grid, hipStream_t st) {
+    if (p.rv_off) hipLaunchKernelGGL((range_kernel<MET, true>), dim3(grid), dim3(kRgWG), 0, st, p);
+    else hipLaunchKernelGGL((range_kernel<MET, false>), dim3(grid), dim3(kRgWG), 0, st, p);
+}
+void launch_range(const RangeParams& p, int met, uint32_t grid, hipStream_t st) {
+    switch (met) {
+        case 0: launch_rg<0>(p, grid, st); break;
+        case 1: launch_rg<1>(p, grid, st); break;
+        case 2: launch_rg<2>(p, grid, st); break;
+        default: launch_rg<3>(p, grid, st); break;
+    }
+}
+
+template <int MET>
+static hipError_t occ_rg(int* n, bool multi) {
+    return multi ? hipOccupancyMaxActiveBlocksPerMultiprocessor(n, range_kernel<MET, true>, kRgWG, 0)
+                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(n, range_kernel<MET, false>, kRgWG, 0);
+}
+int range_occupancy(int met, bool multi) {
+    int n = 0;
+    const hipError_t e = met == 0 ? occ_rg<0>(&n, multi) : met == 1 ? occ_rg<1>(&n, multi) : met == 2 ? occ_rg<2>(&n, multi)
+                                                                                            : occ_rg<3>(&n, multi);
+    return e == hipSuccess && n > 0 ? n : 1;
+}
+
+}  // namespace esgpu

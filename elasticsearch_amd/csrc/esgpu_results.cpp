@@ -273,7 +273,7 @@ Block Block::like() const {
     b.time_zone = time_zone; b.value_format = value_format; b.format = format;
     b.terms_kind = terms_kind;
     b.n = 0;
-    if (is_bucket()) {
+    if (has_buckets()) {
         b.boff.assign(1, 0);
         b.term_off.assign(1, 0);
         for (const Block& s : subs) b.subs.push_back(s.like());
@@ -286,7 +286,7 @@ Block Block::like() const {
 
 void Block::append_instance(const Block& src, uint64_t i) {
     ++n;
-    if (is_bucket()) {
+    if (has_buckets()) {
         doc_count_error.push_back(src.doc_count_error[i]);
         other_doc_count.push_back(src.other_doc_count[i]);
         const uint64_t b0 = src.boff[i], b1 = src.boff[i + 1];
@@ -295,6 +295,7 @@ void Block::append_instance(const Block& src, uint64_t i) {
             term_pool.append(src.term_pool, src.term_off[k], src.term_off[k + 1] - src.term_off[k]);
             term_off.push_back(term_pool.size());
             if (terms_kind == 1) term_long.push_back(src.long_key(k));
+            if (is_range()) { rfrom.push_back(src.rfrom[k]); rto.push_back(src.rto[k]); }
             bcount.push_back(src.bcount[k]);
             berr.push_back(src.berr[k]);
         }
@@ -320,7 +321,7 @@ void Block::append_instance(const Block& src, uint64_t i) {
 
 void Block::append_empty() {  // buildEmptyAggregation
     ++n;
-    if (is_bucket()) {
+    if (has_buckets()) {  // (a range is top level and built with all its ranges by the plan: never appended empty there)
         doc_count_error.push_back(0);
         other_doc_count.push_back(0);
         boff.push_back(boff.back());
@@ -986,6 +987,43 @@ void reduce_level(const Level& lv, Block& out) {
             if (!fused_leaf(out.subs[j])) reduce_level(child[j], out.subs[j]);
         return;
     }
+    if (out.is_range()) {  // InternalRange.doReduce (:290-311): by position -- doc counts add, the buckets' subs reduce
+        std::vector<Level> child(out.subs.size());
+        std::vector<Ref> rs;
+        for (const Group& g : lv.groups) {
+            const Ref* refs = lv.pool.data() + g.begin;
+            const size_t n = g.end - g.begin;
+            const Block& f = *refs[0].b;
+            const uint64_t f0 = f.boff[refs[0].i], R = f.boff[refs[0].i + 1] - f0;
+            for (size_t x = 1; x < n; ++x) {
+                const Block& s = *refs[x].b;
+                if (s.boff[refs[x].i + 1] - s.boff[refs[x].i] != R)
+                    throw std::invalid_argument("range aggregation [" + out.name + "]: shards carry different numbers of ranges");
+            }
+            ++out.n;
+            out.doc_count_error.push_back(0);
+            out.other_doc_count.push_back(0);
+            for (uint64_t k = 0; k < R; ++k) {  // key, from, to: the first shard's bucket (rangeList[i].get(0))
+                int64_t dc = 0;
+                for (size_t x = 0; x < n; ++x) dc += refs[x].b->bcount[refs[x].b->boff[refs[x].i] + k];
+                out.key.push_back((int64_t)k);
+                out.term_pool.append(f.term_pool, f.term_off[f0 + k], f.term_off[f0 + k + 1] - f.term_off[f0 + k]);
+                out.term_off.push_back(out.term_pool.size());
+                out.rfrom.push_back(f.rfrom[f0 + k]);
+                out.rto.push_back(f.rto[f0 + k]);
+                out.bcount.push_back(dc);
+                out.berr.push_back(0);
+                for (size_t j = 0; j < out.subs.size(); ++j) {
+                    rs.clear();
+                    for (size_t x = 0; x < n; ++x) rs.push_back({&refs[x].b->subs[j], refs[x].b->boff[refs[x].i] + k});
+                    child[j].add(rs.data(), rs.size(), g.verbatim);
+                }
+            }
+            out.boff.push_back(out.boff.back() + R);
+        }
+        for (size_t j = 0; j < out.subs.size(); ++j) reduce_level(child[j], out.subs[j]);
+        return;
+    }
     if (out.type == ESGPU_AGG_FILTER) {  // InternalFilter (InternalSingleBucketAggregation.doReduce): Σ doc_count, subs
         std::vector<Level> child(out.subs.size());
         std::vector<Ref> rs;
@@ -1255,6 +1293,21 @@ void write_instance(J& j, const Block& a, uint64_t i) {
             j.key("doc_count"); j.i64(a.count[i]);
             write_subs(j, a, i);
             break;
+        case ESGPU_AGG_RANGE:  // every range, in bucket order; from / to only for finite sides
+            j.key("buckets"); j.raw("[");
+            for (uint64_t k = a.boff[i]; k < a.boff[i + 1]; ++k) {
+                if (k != a.boff[i]) j.raw(",");
+                j.raw("{"); j.key("key");
+                j.str(a.term_pool.data() + a.term_off[k], a.term_off[k + 1] - a.term_off[k]);
+                j.raw(",");
+                if (!std::isinf(a.rfrom[k])) { j.key("from"); j.dbl(a.rfrom[k]); j.raw(","); }
+                if (!std::isinf(a.rto[k])) { j.key("to"); j.dbl(a.rto[k]); j.raw(","); }
+                j.key("doc_count"); j.i64(a.bcount[k]);
+                write_subs(j, a, k);
+                j.raw("}");
+            }
+            j.raw("]");
+            break;
         case ESGPU_AGG_AVG:
             j.key("value"); j.opt(a.count[i] != 0, a.sum[i] / (double)a.count[i]);
             j.raw(","); j.key("_internal"); j.raw("{"); j.key("count"); j.i64(a.count[i]); j.raw(",");
@@ -1464,6 +1517,27 @@ void x_instance(X& x, const Block& a, uint64_t i) {
             x.key("doc_count"); x.i64(a.count[i]);
             x_subs(x, a, i);
             break;
+        case ESGPU_AGG_RANGE:  // InternalRange.doXContentBody (:339-355), Bucket.toXContent (InternalRange.java:166-190)
+            x.key("buckets"); x.raw(a.keyed ? "{" : "[");
+            for (uint64_t k = a.boff[i]; k < a.boff[i + 1]; ++k) {
+                if (k != a.boff[i]) x.raw(",");
+                const std::string rk = a.term(k);
+                if (a.keyed) { x.key(rk); x.raw("{"); }
+                else { x.raw("{"); x.key("key"); x.str(rk); x.raw(","); }
+                if (!std::isinf(a.rfrom[k])) {
+                    x.key("from"); x.dbl(a.rfrom[k]); x.raw(",");
+                    x.key("from_as_string"); x.str(range_bound_string(a.value_format, a.rfrom[k])); x.raw(",");
+                }
+                if (!std::isinf(a.rto[k])) {
+                    x.key("to"); x.dbl(a.rto[k]); x.raw(",");
+                    x.key("to_as_string"); x.str(range_bound_string(a.value_format, a.rto[k])); x.raw(",");
+                }
+                x.key("doc_count"); x.i64(a.bcount[k]);
+                x_subs(x, a, k);
+                x.raw("}");
+            }
+            x.raw(a.keyed ? "}" : "]");
+            break;
         case ESGPU_AGG_AVG:
             x.key("value"); x.opt(a.count[i] != 0, a.sum[i] / (double)a.count[i]);
             break;
@@ -1510,6 +1584,47 @@ void x_instance(X& x, const Block& a, uint64_t i) {
     x.raw("}");
 }
 }  // namespace
+
+// ValueFormatter.format(double) of a range bound: Raw prints String.valueOf(double) (ValueFormatter.java:96-99), DateTime
+// the field's printer over (long) value in UTC (:139-147; Java's cast: saturating)
+std::string range_bound_string(int32_t value_format, double v) {
+    if (value_format == ESGPU_FORMAT_DATE_TIME) {
+        const int64_t ms = v != v ? 0 : v >= 9223372036854775807.0 ? INT64_MAX : v <= -9223372036854775808.0 ? INT64_MIN : (int64_t)v;
+        return es_date(ms, {}, {});
+    }
+    return java_double(v);
+}
+
+std::vector<RangeBucket> range_buckets(const esgpu_agg_spec& spec) {
+    if (spec.n_ranges <= 0 || !spec.ranges) throw std::invalid_argument("No [ranges] specified for the [range] aggregation");
+    if (spec.n_ranges > 64) throw std::domain_error("a range aggregation over more than 64 ranges runs on the CPU path");
+    if (spec.value_format == ESGPU_FORMAT_NUMBER)
+        throw std::domain_error("a range aggregation with a number format runs on the CPU path");
+    if (spec.value_format == ESGPU_FORMAT_DATE_TIME) {
+        const std::string f = spec.format ? spec.format : "";
+        if (!(f.empty() || f == "strict_date_optional_time" || f == "strict_date_optional_time||epoch_millis"))
+            throw std::domain_error("a range aggregation with the date format [" + f + "] runs on the CPU path");
+    } else if (spec.value_format != ESGPU_FORMAT_RAW) {
+        throw std::invalid_argument("unknown value format");
+    }
+    std::vector<RangeBucket> out;
+    for (int32_t i = 0; i < spec.n_ranges; ++i) {
+        const esgpu_range& r = spec.ranges[i];
+        if (r.from != r.from || r.to != r.to) throw std::invalid_argument("a range bound of the [range] aggregation is NaN");
+        out.push_back(RangeBucket{i, r.from, r.to, r.key ? std::string(r.key) : std::string()});
+        if (!r.key) {
+            RangeBucket& b = out.back();
+            b.key = (std::isinf(r.from) ? std::string("*") : range_bound_string(spec.value_format, r.from)) + "-" +
+                    (std::isinf(r.to) ? std::string("*") : range_bound_string(spec.value_format, r.to));
+        }
+    }
+    auto cmp = [](double a, double b) { return compare_discard_nan(a, b, true); };  // Double.compare (no NaN here)
+    std::stable_sort(out.begin(), out.end(), [&](const RangeBucket& a, const RangeBucket& b) {
+        const int c = cmp(a.from, b.from);
+        return c != 0 ? c < 0 : cmp(a.to, b.to) < 0;
+    });
+    return out;
+}
 
 std::string to_xcontent(const std::vector<Block>& aggs) {
     X x;
@@ -1594,6 +1709,7 @@ const char* stream_type(int32_t type) {  // InternalAggregation.Type stream name
         case ESGPU_AGG_VALUE_COUNT: return "value_count";    // InternalValueCount.java:40
         case ESGPU_AGG_CARDINALITY: return "cardinality";    // InternalCardinality.java:39
         case ESGPU_AGG_FILTER: return "filter";              // InternalFilter.java:36
+        case ESGPU_AGG_RANGE: return "range";                // InternalRange.java:44
     }
     throw std::invalid_argument("aggregation type without a stream");
 }
@@ -1765,6 +1881,21 @@ void es_instance(JavaOut& w, const Block& a, uint64_t i) {
             w.vlong(a.count[i]);
             es_list(w, a.subs, i);
             break;
+        case ESGPU_AGG_RANGE: {  // InternalRange.doWriteTo (:323-337)
+            write_formatter(w, a);
+            w.boolean(a.keyed != 0);
+            const uint64_t b0 = a.boff[i], b1 = a.boff[i + 1];
+            w.vint((int32_t)(b1 - b0));
+            for (uint64_t b = b0; b < b1; ++b) {
+                w.boolean(true);  // writeOptionalString: a bucket always has its key (given or generated)
+                w.str(a.term(b));
+                w.f64(a.rfrom[b]);
+                w.f64(a.rto[b]);
+                w.vlong(a.bcount[b]);
+                es_list(w, a.subs, b);
+            }
+            break;
+        }
         default: throw std::invalid_argument("aggregation type without a stream");
     }
 }
@@ -1838,6 +1969,7 @@ void w_block(W& w, const Block& a) {
     w.vec(a.doc_count_error); w.vec(a.other_doc_count); w.vec(a.boff); w.vec(a.key); w.vec(a.term_off);
     w.str(a.term_pool); w.vec(a.bcount); w.vec(a.berr);
     if (w.version >= 6) { w.pod(a.terms_kind); w.vec(a.term_long); }
+    if (w.version >= 7) { w.vec(a.rfrom); w.vec(a.rto); }
     w_blocks(w, a.subs);
     w_blocks(w, a.empty_subs);
     w.vec(a.count); w.vec(a.sum); w.vec(a.min); w.vec(a.max); w.vec(a.sumsq);
@@ -1867,6 +1999,7 @@ void r_block(R& r, Block& a, int depth) {
     r.vec(a.doc_count_error); r.vec(a.other_doc_count); r.vec(a.boff); r.vec(a.key); r.vec(a.term_off);
     a.term_pool = r.str(); r.vec(a.bcount); r.vec(a.berr);
     if (r.version >= 6) { a.terms_kind = r.pod<int32_t>(); r.vec(a.term_long); }
+    if (r.version >= 7) { r.vec(a.rfrom); r.vec(a.rto); }
     r_blocks(r, a.subs, depth + 1);
     r_blocks(r, a.empty_subs, depth + 1);
     r.vec(a.count); r.vec(a.sum); r.vec(a.min); r.vec(a.max); r.vec(a.sumsq);
@@ -1876,7 +2009,10 @@ void r_block(R& r, Block& a, int depth) {
     a.lc.resize(r.pod<uint64_t>());
     for (auto& x : a.lc) r.vec(x);
     // structural validation: a corrupt record must not produce out-of-bounds views
-    const bool bucket = a.is_bucket();
+    const bool bucket = a.has_buckets();
+    if (a.rfrom.size() != (a.is_range() ? a.nbuckets() : 0) || a.rto.size() != a.rfrom.size())
+        throw std::runtime_error("inconsistent range bounds");
+    if (a.is_range() && !a.empty_subs.empty()) throw std::runtime_error("empty-bucket prototypes on a range block");
     if (!bucket && (a.terms_kind != 0 || !a.term_long.empty())) throw std::runtime_error("long terms fields on a block without buckets");
     if (bucket) {
         const uint64_t nb = a.boff.empty() ? 0 : a.boff.back();
@@ -1929,7 +2065,13 @@ void r_blocks(R& r, std::vector<Block>& l, int depth) {
 }
 const uint32_t kStreamMagic = 0x45534750;  // "ESGP"
 // version 6 = version 5 plus, per block, the terms kind and the long keys; written only when a result holds LongTerms
-const uint32_t kStreamVersion = 5, kStreamVersionLongTerms = 6;
+// version 7 = version 6 plus, per block, the range bounds; written only when a result holds a range block
+const uint32_t kStreamVersion = 5, kStreamVersionLongTerms = 6, kStreamVersionRange = 7;
+bool has_range(const std::vector<Block>& l) {
+    for (const Block& a : l)
+        if (a.is_range() || has_range(a.subs) || has_range(a.empty_subs)) return true;
+    return false;
+}
 bool has_long_terms(const std::vector<Block>& l) {
     for (const Block& a : l)
         if (a.terms_kind == 1 || has_long_terms(a.subs) || has_long_terms(a.empty_subs)) return true;
@@ -1940,7 +2082,7 @@ bool has_long_terms(const std::vector<Block>& l) {
 void serialize(const std::vector<Block>& aggs, std::string& out) {
     out.clear();
     W w{out};
-    w.version = has_long_terms(aggs) ? kStreamVersionLongTerms : kStreamVersion;
+    w.version = has_range(aggs) ? kStreamVersionRange : has_long_terms(aggs) ? kStreamVersionLongTerms : kStreamVersion;
     w.pod(kStreamMagic);
     w.pod(w.version);
     w_blocks(w, aggs);
@@ -1950,7 +2092,7 @@ bool deserialize(const uint8_t* p, size_t n, std::vector<Block>& out) {
     R r{p, n};
     if (n < 8 || r.pod<uint32_t>() != kStreamMagic) return false;
     r.version = r.pod<uint32_t>();
-    if (r.version != kStreamVersion && r.version != kStreamVersionLongTerms) return false;
+    if (r.version != kStreamVersion && r.version != kStreamVersionLongTerms && r.version != kStreamVersionRange) return false;
     r_blocks(r, out, 0);
     for (const Block& b : out) if (b.n != 1) throw std::runtime_error("top-level aggregations carry one instance");
     return true;
@@ -1992,6 +2134,8 @@ void export_block(ResultHolder& h, const Block& a, esgpu_agg_block& o) {
     o.format = a.format.c_str();
     o.terms_kind = a.terms_kind;
     o.term_longs = ptr(a.term_long);
+    o.range_from = ptr(a.rfrom);
+    o.range_to = ptr(a.rto);
     o.nsubs = (int32_t)a.subs.size();
     o.n_instances = a.n;
     o.doc_count_error = ptr(a.doc_count_error);

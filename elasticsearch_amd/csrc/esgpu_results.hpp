@@ -56,6 +56,7 @@ struct Block {
     std::string term_pool;
     int32_t terms_kind = 0;                // terms: 0 = StringTerms, 1 = LongTerms (a long / date field)
     std::vector<int64_t> term_long;        // [nb] terms_kind 1: the key (term_pool holds its decimal text)
+    std::vector<double> rfrom, rto;        // [nb] range: the bucket's bounds (its key in term_pool; `key` = its position)
     std::vector<int64_t> bcount;           // [nb] doc_count
     std::vector<int64_t> berr;             // [nb] bucket doc_count_error
     std::vector<Block> subs;               // each with n == nb
@@ -73,6 +74,10 @@ struct Block {
 
     Rounding rounding() const;  // histogram specs: the request's Rounding (EmptyBucketInfo)
     bool is_bucket() const { return type == ESGPU_AGG_TERMS || type == ESGPU_AGG_HISTOGRAM || type == ESGPU_AGG_DATE_HISTOGRAM; }
+    // range (InternalRange): buckets in the flat arrays like the bucket aggregations above, every instance with all the
+    // request's ranges; reduced by position, so it is kept apart from is_bucket()'s key-merging reduces
+    bool is_range() const { return type == ESGPU_AGG_RANGE; }
+    bool has_buckets() const { return is_bucket() || is_range(); }
     uint64_t nbuckets() const { return boff.empty() ? 0 : boff.back(); }
     // terms_kind 1: bucket b's key.  A StringTerms block met where LongTerms are reduced (a field mapped as keyword on
     // one shard and as long on another, or an old result) fails the reduce like every other mismatch of the trees.
@@ -96,6 +101,19 @@ struct Block {
 // values (null: the segment lacks the field) in numeric order, and per segment its local -> global ordinal table.
 void merge_long_dicts(const std::vector<const std::vector<int64_t>*>& segs, std::vector<int64_t>& global,
                       std::vector<std::vector<uint32_t>>& maps);
+
+// The buckets of a range spec (RangeAggregator.java:96-119, InternalRange.Bucket.generateKey): the ranges sorted stably by
+// (from, to) in Double.compare order, each with its key -- the given one, or "*" / the formatter's text of each bound
+// (RAW: Double.toString; DATE_TIME: the date printer over (long) bound, UTC).  Throws std::invalid_argument for no ranges / a NaN bound, std::domain_error for what stays on the CPU path (more than 64
+// ranges, a number pattern, a date format the printer does not print).
+struct RangeBucket {
+    int32_t src;      // index into spec.ranges
+    double from, to;
+    std::string key;
+};
+std::vector<RangeBucket> range_buckets(const esgpu_agg_spec& spec);
+// ValueFormatter.format(bound) of a range block (from_as_string / to_as_string)
+std::string range_bound_string(int32_t value_format, double v);
 
 // sum / min / max / value_count: single-value numeric metrics whose block fills one of the stats arrays (sum -> sum,
 // min -> min, max -> max, value_count -> count)

@@ -895,6 +895,29 @@ extern "C" int esgpu_date_rounding(const esgpu_agg_spec* spec, int32_t op, int64
     });
 }
 
+extern "C" int esgpu_range_buckets(const esgpu_agg_spec* spec, int32_t* order_out, char* keys_buf, size_t cap, size_t* needed) {
+    return guarded([&] {
+        require(spec != nullptr, ESGPU_ERR_INVALID, "null argument");
+        require(spec->type == ESGPU_AGG_RANGE, ESGPU_ERR_INVALID, "not a range spec");
+        std::vector<RangeBucket> rb;
+        try {
+            rb = range_buckets(*spec);
+        } catch (const std::domain_error& e) {
+            throw EsError(ESGPU_ERR_UNSUPPORTED, e.what());
+        } catch (const std::invalid_argument& e) {
+            throw EsError(ESGPU_ERR_INVALID, e.what());
+        }
+        std::string keys;
+        for (size_t b = 0; b < rb.size(); ++b) {
+            if (order_out) order_out[b] = rb[b].src;
+            keys += rb[b].key;
+            keys.push_back('\0');
+        }
+        if (needed) *needed = keys.size();
+        if (keys_buf && cap) std::memcpy(keys_buf, keys.data(), std::min(cap, keys.size()));
+    });
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // index-time hashing (bulk ingest helpers)
 // ------------------------------------------------------------------------------------------------------------
@@ -978,6 +1001,7 @@ struct SpecNode {
     int precision = 14;
     std::vector<int64_t> tz_starts, tz_offs;  // owned copy of the spec's time zone table
     std::string time_zone = "UTC", format;    // wire-stream parameters (esgpu_agg_spec.time_zone / format)
+    std::vector<RangeBucket> rbuckets;        // range: its buckets in result order (range_buckets)
     Rounding rounding() const {               // histogram specs (Rounding.java / TimeZoneRounding.java)
         esgpu_agg_spec sp = s;
         sp.tz_count = (int32_t)tz_starts.size();
@@ -1017,6 +1041,13 @@ struct Pipeline {
     int kind = 0;              // 0 = cell grid (bucket / metric), 1 = cardinality
     int fspec = -1;            // enclosing filter aggregation (FilterAggregator): its clauses apply too; -1 = none
     bool count_only = false;   // the filter aggregation's own doc_count (one cell, no metric)
+    // a range aggregation's pipeline (collect path 11): the grid is [1][R] cells, one per range in bucket order, filled by
+    // range_kernel from the range field and the pipeline's metric field; rtable: the device table of the ranges' cuts
+    // and masks (RangeParams.table) as made for a long (1) or a double (2) range column
+    bool range = false;
+    std::string range_field;
+    DevBuf d_rtable;
+    int rtable_kind = 0;
     // cell grid shape
     int outer = -1, inner = -1;      // bucket spec indices (inner may be -1)
     int term_spec = -1, hist_spec = -1;
@@ -1280,6 +1311,11 @@ static int add_pipeline(esgpu_plan* p, int root, int fspec, int outer, int inner
     for (int b : {outer, inner}) {
         if (b < 0) continue;
         const SpecNode& n = p->specs[b];
+        if (n.s.type == ESGPU_AGG_RANGE) {  // (top level, metric leaves only: no inner dimension)
+            pl.range = true;
+            pl.range_field = n.field;
+            continue;
+        }
         if (n.s.type == ESGPU_AGG_TERMS && b == inner && outer >= 0 && p->specs[outer].s.type == ESGPU_AGG_TERMS) {
             // terms under terms: the inner field's ordinals are the key dimension (key = ordinal)
             pl.hist_spec = b;
@@ -1333,7 +1369,9 @@ static int add_pipeline(esgpu_plan* p, int root, int fspec, int outer, int inner
         pl.met = std::max(pl.met, metric_level(n.s.type));
         pl.sums = pl.sums || metric_has_sum(n.s.type);
     }
-    if (pl.met == 0 && !pl.metric_field.empty()) {  // value_count leaves only (the product's sums are read)
+    if (pl.range && pl.met == 0 && !pl.metric_field.empty()) {
+        pl.met = 1;  // value_count leaves alone under a range: counted as the field's values are streamed (no product)
+    } else if (pl.met == 0 && !pl.metric_field.empty()) {  // value_count leaves only (the product's sums are read)
         pl.vc_only = true;
         pl.sums = true;
     }
@@ -1394,6 +1432,20 @@ static Group compile_group(esgpu_plan* p, int r, int fspec) {
     }
     if (is_metric(root.s.type)) {
         g.pipes.push_back(add_pipeline(p, r, fspec, -1, -1, {r}));
+        return g;
+    }
+    if (root.s.type == ESGPU_AGG_RANGE) {
+        // RangeAggregator: its metric children grouped by field, one pipeline (one pass over the range field and that
+        // metric field) each; every pipeline counts the ranges' docs alike and pipes[0]'s counts are the doc counts.  A
+        // range without children gets one counting pipeline.
+        std::vector<LeafRef> refs;
+        g.pipes = add_leaf_pipelines(p, r, fspec, r, -1, root.children, &refs);
+        for (size_t j = 0; j < root.children.size(); ++j) {
+            ChildSrc cs;
+            cs.spec = root.children[j];
+            cs.leaf = refs[j];
+            g.kids.push_back(std::move(cs));
+        }
         return g;
     }
     require(is_bucket(root.s.type), ESGPU_ERR_UNSUPPORTED, "aggregation type not on the GPU path");
@@ -1528,7 +1580,19 @@ extern "C" int esgpu_plan_create(esgpu_ctx* c, const esgpu_agg_spec* specs, int3
             }
             n.s.time_zone = nullptr;
             n.s.format = nullptr;
-            require(n.s.type >= ESGPU_AGG_TERMS && n.s.type <= ESGPU_AGG_FILTER, ESGPU_ERR_INVALID, "unknown aggregation type");
+            require(n.s.type >= ESGPU_AGG_TERMS && n.s.type <= ESGPU_AGG_RANGE, ESGPU_ERR_INVALID, "unknown aggregation type");
+            if (n.s.type == ESGPU_AGG_RANGE) {
+                try {
+                    n.rbuckets = range_buckets(specs[i]);
+                } catch (const std::domain_error& e) {
+                    throw EsError(ESGPU_ERR_UNSUPPORTED, std::string(e.what()) + " [" + n.name + "]");
+                } catch (const std::invalid_argument& e) {
+                    throw EsError(ESGPU_ERR_INVALID, std::string(e.what()) + " [" + n.name + "]");
+                }
+                require(n.s.parent < 0, ESGPU_ERR_UNSUPPORTED,
+                        "a range aggregation below the top level runs on the CPU path [" + n.name + "]");
+            }
+            n.s.ranges = nullptr;
             if (n.s.type == ESGPU_AGG_FILTER && n.s.parent >= 0) {
                 // a chain of filter aggregations from the top (each one's docs: its clauses and its ancestors'), or a
                 // filter directly under a bucket aggregation of the first bucket level (compile_group)
@@ -1542,7 +1606,10 @@ extern "C" int esgpu_plan_create(esgpu_ctx* c, const esgpu_agg_spec* specs, int3
             else {
                 require(n.s.parent < i, ESGPU_ERR_INVALID, "parent must precede child");
                 const int pt = p->specs[n.s.parent].s.type;
-                require(is_bucket(pt) || pt == ESGPU_AGG_FILTER, ESGPU_ERR_INVALID, "metrics aggregations cannot have sub-aggregations");
+                require(is_bucket(pt) || pt == ESGPU_AGG_FILTER || pt == ESGPU_AGG_RANGE, ESGPU_ERR_INVALID,
+                        "metrics aggregations cannot have sub-aggregations");
+                require(pt != ESGPU_AGG_RANGE || is_metric(n.s.type), ESGPU_ERR_UNSUPPORTED,
+                        "a range aggregation with a bucket, filter or cardinality sub-aggregation runs on the CPU path");
                 p->specs[n.s.parent].children.push_back(i);
             }
             if (n.s.type == ESGPU_AGG_TERMS) {
@@ -3009,7 +3076,191 @@ static void collect_cards(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, c
 // 0 = nothing collected, 1 = the grid, 2 = only the outer doc counts (the segment lacks the inner dimension's field)
 static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, const uint64_t* d_accept);
 
+// The device table of a range aggregation's buckets (RangeParams.table) for a long or a double range column: the
+// distinct finite bounds as ascending cuts, and per elementary interval the mask of the buckets that hold it.  Every
+// finite bound is a cut, so an interval lies wholly inside or outside each range: bucket i holds interval k, the values
+// between cut k - 1 and cut k, iff from_i <= cut k - 1 (-inf for k = 0) and to_i >= cut k (+inf past the last cut) --
+// which no range with from >= to satisfies.
+//   double column: the cuts are the keys the kernel compares doubles by (rg_key: the bits, sign-folded; the bound 0.0 as
+//                  the key of -0.0, so that both zeros reach it, as value >= 0.0 does).
+//   long column:   the reference compares (double) value; rounding to double is monotone, so (double) v >= bound is
+//                  v >= L for L the least long whose double reaches the bound -- found by bisection over the longs.  A
+//                  bound no long reaches ends the table: the values of the last interval then stay below every later cut.
+static void build_range_table(const std::vector<RangeBucket>& rb, bool f64, std::vector<uint64_t>& table, uint32_t* n_cuts) {
+    std::vector<double> cuts;
+    for (const RangeBucket& b : rb)
+        for (double v : {b.from, b.to})
+            if (!std::isinf(v)) cuts.push_back(v == 0.0 ? 0.0 : v);  // (-0.0 and 0.0 are one bound)
+    std::sort(cuts.begin(), cuts.end());
+    cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+    table.assign((size_t)kRangeCuts + kRangeCuts + 1, 0);
+    uint32_t n = 0;
+    for (double c : cuts) {
+        if (f64) {
+            int64_t b;
+            const double z = c == 0.0 ? -0.0 : c;
+            std::memcpy(&b, &z, 8);
+            table[n++] = (uint64_t)(b ^ ((b >> 63) & 0x7FFFFFFFFFFFFFFFll));
+            continue;
+        }
+        if (!((double)INT64_MAX >= c)) break;  // (double) Long.MAX_VALUE = 2^63: no long reaches a bound above it
+        // least L with (double) L >= c, over the longs in their unsigned-offset order
+        uint64_t lo = 0, hi = ~0ull;  // the predicate holds at hi
+        auto val = [](uint64_t u) { return (int64_t)(u ^ 0x8000000000000000ull); };
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if ((double)val(mid) >= c) hi = mid; else lo = mid + 1;
+        }
+        table[n++] = (uint64_t)val(lo);
+    }
+    for (uint32_t k = 0; k <= n; ++k) {
+        const double lo = k == 0 ? -INFINITY : cuts[k - 1], hi = k < cuts.size() ? cuts[k] : INFINITY;
+        uint64_t m = 0;
+        for (size_t i = 0; i < rb.size(); ++i)
+            if (rb[i].from <= lo && rb[i].to >= hi && rb[i].from < rb[i].to) m |= 1ull << i;
+        table[kRangeCuts + k] = m;
+    }
+    *n_cuts = n;
+}
+
+// RangeAggregator's collect of one segment (collect path 11): one launch of range_kernel over the range field and the
+// pipeline's metric field into the pipeline's [1][R] grid.  The query clauses and the accept bits are folded into one
+// doc bitset first (launch_filter_bits); the kernel evaluates no clause.
+static bool collect_range(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, const uint64_t* d_accept) {
+    const SpecNode& rn = p->specs[pl.outer];
+    const DevColumn* rc = s->col(pl.range_field.c_str());
+    if (!rc) return false;  // a segment without the field contributes nothing (ValuesSource null)
+    require(rc->type == ESGPU_COL_I64 || rc->type == ESGPU_COL_F64, ESGPU_ERR_UNSUPPORTED,
+            "range over a keyword or murmur3 field runs on the CPU path");
+    const DevColumn* mc = pl.met > 0 ? s->col(pl.metric_field.c_str()) : nullptr;
+    if (mc) {
+        require(mc->type == ESGPU_COL_I64 || mc->type == ESGPU_COL_F64, ESGPU_ERR_UNSUPPORTED,
+                "a metric over a non-numeric field under a range runs on the CPU path");
+        require(!mc->multi, ESGPU_ERR_UNSUPPORTED, "a multi-valued metric field under a range runs on the CPU path");
+    }
+    const uint32_t n_blocks = s->n_pad / kBlockDocs;
+    if (n_blocks == 0) return false;
+    const uint32_t R = (uint32_t)rn.rbuckets.size();
+    // (an unmapped metric field collects nothing: the doc counts alone, and the value counts split from them)
+    const bool sparse_metric = pl.met > 0 && (!mc || mc->present.p);
+    const bool first_segment = !pl.allocated || pl.fresh;
+    if (first_segment) {
+        const int vcnt = sparse_metric ? 1 : 0;
+        const bool same = pl.allocated && pl.T == R && pl.H == 1 && vcnt == pl.vcnt_mode;
+        pl.T = R;
+        pl.H = 1;
+        pl.key0 = 0;
+        pl.vcnt_mode = vcnt;
+        pl.ocnt_mode = OCNT_NONE;
+        pl.keyed = false;
+        pl.value_count = R;
+        if (!same) alloc_grid(p, pl);
+        pl.fresh = false;
+        pl.dd = false;
+        pl.dd_vals = 0;
+        pl.dd_amax = 0;
+    } else if (sparse_metric && !pl.vcnt_mode) {
+        // the metric field turns sparse in this segment: the value counts split from the doc counts they equalled so far
+        zero_counts(p, pl);
+        pl.g_vcnt.alloc(p->ctx, (size_t)R * 8);
+        HIPX(hipMemcpyAsync(pl.g_vcnt.p, pl.g_cnt.p, (size_t)R * 8, hipMemcpyDeviceToDevice, p->stream));
+        pl.vcnt_mode = 1;
+    }
+    zero_counts(p, pl);
+    const int kind = rc->type == ESGPU_COL_F64 ? 2 : 1;
+    RangeParams P{};
+    {
+        std::vector<uint64_t> table;
+        build_range_table(rn.rbuckets, kind == 2, table, &P.n_cuts);
+        if (pl.rtable_kind != kind) {
+            if (!pl.d_rtable.p) pl.d_rtable.alloc(p->ctx, table.size() * 8);
+            HIPX(hipMemcpyAsync(pl.d_rtable.p, table.data(), table.size() * 8, hipMemcpyHostToDevice, p->stream));
+            HIPX(hipStreamSynchronize(p->stream));  // (the host table goes out of scope)
+            pl.rtable_kind = kind;
+        }
+    }
+    P.table = pl.d_rtable.as<uint64_t>();
+    P.R = R;
+    P.rv = rc->multi ? rc->values.p : wide_i64(p->ctx, rc, s, p->stream);  // (released upload-width values are rebuilt)
+    P.rv_present = rc->multi ? nullptr : rc->present.as<uint64_t>();
+    P.rv_off = rc->multi ? rc->offsets.as<uint64_t>() : nullptr;
+    P.rv_f64 = kind == 2;
+    const int met = mc ? pl.met : 0;
+    if (mc) {
+        P.mv = wide_i64(p->ctx, mc, s, p->stream);
+        P.mv_present = mc->present.as<uint64_t>();
+        P.mv_f64 = mc->type == ESGPU_COL_F64;
+    }
+    P.vcnt_mode = met > 0 ? pl.vcnt_mode : 0;
+    P.n_docs = s->max_doc;
+    P.n_blocks = n_blocks;
+    P.g_cnt = pl.g_cnt.as<unsigned long long>();
+    P.g_vcnt = pl.g_vcnt.as<unsigned long long>();
+    P.g_sum = pl.g_sum.as<double>();
+    P.g_min = pl.g_min.as<unsigned long long>();
+    P.g_max = pl.g_max.as<unsigned long long>();
+    P.g_sq = pl.g_sq.as<double>();
+    // compensated sums: the rule of the cell-grid collects (collect_grid_cells)
+    if (met > 0 && pl.sums) {
+        pl.dd_vals += (uint64_t)s->max_doc;
+        if (mc->type == ESGPU_COL_F64 || dd_forced()) {
+            pl.dd = true;
+        } else if (mc->vmin <= mc->vmax) {
+            auto mag = [](int64_t v) { return v < 0 ? (uint64_t)0 - (uint64_t)v : (uint64_t)v; };
+            pl.dd_amax = std::max(pl.dd_amax, std::max(mag(mc->vmin), mag(mc->vmax)));
+            const long double n = (long double)pl.dd_vals, a = (long double)pl.dd_amax, lim = 9007199254740992.0L;
+            if (n * a >= lim || (pl.met >= 3 && n * a * a >= lim)) pl.dd = true;
+        }
+    }
+    if (pl.dd && met > 0) {
+        auto lo = [&](DevBuf& b) {
+            if (b.p && b.bytes >= (size_t)R * 8) return b.as<double>();
+            b.alloc(p->ctx, (size_t)R * 8 + (size_t)R * 2);
+            HIPX(hipMemsetAsync(b.p, 0, b.bytes, p->stream));
+            return b.as<double>();
+        };
+        P.g_sum_lo = lo(pl.g_sum_lo);
+        if (met >= 3 && P.g_sq) P.g_sq_lo = lo(pl.g_sq_lo);
+    }
+    // algorithmic bytes: each column at the width read, CSR offsets, the clause columns, the doc bitset
+    uint64_t bytes = rc->multi ? 8ull * rc->n_values + 8ull * s->max_doc : 8ull * s->max_doc;
+    if (mc) bytes += 8ull * s->max_doc;
+    PredDev pred[kMaxPreds];
+    int32_t npred = 0;
+    uint64_t pred_bpd = 0;
+    const uint64_t* accept = d_accept;
+    set_preds(p, pl, s, pred, &npred, &pred_bpd, &accept);
+    bytes += pred_bpd * s->max_doc;
+    HIPX(hipEventRecord(pl.e0, p->stream));
+    if (npred > 0) {
+        uint64_t* bits = (uint64_t*)p->s_fbits.ensure(p->ctx, std::max<size_t>(s->n_pad / 64, 1) * 8);
+        launch_filter_bits(s->max_doc, accept, pred, npred, bits, p->stream);
+        HIPX(hipGetLastError());
+        accept = bits;
+    }
+    P.accept = accept;
+    if (accept) bytes += ((uint64_t)s->max_doc + 7) / 8;
+    const uint64_t okey = ((uint64_t)met << 1) | (rc->multi ? 1u : 0u);
+    if (pl.occ_key != okey) {
+        pl.occ = range_occupancy(met, rc->multi);
+        pl.occ_key = okey;
+    }
+    const uint32_t slots = std::max(1u, (uint32_t)p->ctx->cus * (uint32_t)pl.occ);
+    P.blocks_per_wg = (n_blocks + slots - 1) / slots;
+    const uint32_t grid = (n_blocks + P.blocks_per_wg - 1) / P.blocks_per_wg;
+    launch_range(P, met, grid, p->stream);
+    HIPX(hipGetLastError());
+    if (P.g_sum_lo) launch_dd_fold(P.g_sum, P.g_sum_lo, R, p->stream);
+    if (P.g_sq_lo) launch_dd_fold(P.g_sq, P.g_sq_lo, R, p->stream);
+    HIPX(hipGetLastError());
+    HIPX(hipEventRecord(pl.e1, p->stream));
+    p->last_bytes += bytes;
+    p->last_path = 11;
+    return true;
+}
+
 static bool collect_grid(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, const uint64_t* d_accept) {
+    if (pl.range) return collect_range(p, pl, s, d_accept);
     const int done = collect_grid_cells(p, pl, s, d_accept);
     if (done == 1 && !pl.cards.empty()) collect_cards(p, pl, s, d_accept);
     return done != 0;
@@ -6285,10 +6536,45 @@ static Block build_hist_root(esgpu_plan* p, const Group& g) {
 
 static Block build_cardinality(esgpu_plan* p, Pipeline& pl);
 
+// RangeAggregator.buildAggregation (:198-209) / buildEmptyAggregation (:212-223): every range a bucket, in bucket order,
+// with its doc count (pipes[0]'s cells) and its leaves from their pipelines' cells -- cell == bucket position
+static Block build_range_root(esgpu_plan* p, const Group& g) {
+    const SpecNode& n = p->specs[g.root];
+    Block r;
+    r.type = ESGPU_AGG_RANGE;
+    r.name = n.name;
+    r.keyed = n.s.keyed;
+    set_format(r, n);
+    r.boff.assign(1, 0);
+    r.term_off.assign(1, 0);
+    for (const Block& b : child_protos(p, g)) r.subs.push_back(b.like());
+    for (int pi : g.pipes) {
+        Pipeline& pl = p->pipes[pi];
+        if (pl.allocated) fetch_grid(p, pl);
+    }
+    bsync(p);
+    const Pipeline& P0 = p->pipes[g.pipes[0]];
+    begin_instance(r, 0);
+    for (size_t k = 0; k < n.rbuckets.size(); ++k) {
+        const RangeBucket& rb = n.rbuckets[k];
+        push_bucket(r, (int64_t)k, &rb.key, P0.allocated ? (int64_t)P0.hc.cnt[k] : 0);
+        r.rfrom.push_back(rb.from);
+        r.rto.push_back(rb.to);
+        for (size_t ki = 0; ki < g.kids.size(); ++ki) {
+            const Pipeline& L = p->pipes[g.kids[ki].leaf.pipe];
+            if (L.allocated) append_leaf(p, L, g.kids[ki].leaf.leaf, k, r.subs[ki]);
+            else r.subs[ki].append_empty();
+        }
+    }
+    end_instance(r);
+    return r;
+}
+
 static Block build_group(esgpu_plan* p, const Group& g) {
     Pipeline& P0 = p->pipes[g.pipes[0]];
     if (P0.kind == 1) return build_cardinality(p, P0);
     const int t = p->specs[g.root].s.type;
+    if (t == ESGPU_AGG_RANGE) return build_range_root(p, g);
     if (is_metric(t)) return build_metric_root(p, g);
     if (t == ESGPU_AGG_TERMS) return build_terms_root(p, g);
     return build_hist_root(p, g);

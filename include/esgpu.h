@@ -237,9 +237,32 @@ enum {
     ESGPU_AGG_MIN = 9,
     ESGPU_AGG_MAX = 10,
     ESGPU_AGG_VALUE_COUNT = 11,
-    ESGPU_AGG_FILTER = 12         /* FilterAggregator: single bucket of the docs matching its clauses (esgpu_filter.owner);
+    ESGPU_AGG_FILTER = 12,        /* FilterAggregator: single bucket of the docs matching its clauses (esgpu_filter.owner);
                                      top level only; result block: count[i] = doc_count, subs = its sub-aggregations */
+    /* RangeAggregator (A/bucket/range/RangeAggregator.java): esgpu_agg_spec.ranges over a long / date / double field
+     * (dense, sparse or multi-valued).  A doc belongs to range i iff one of its values v has (double) v >= from &&
+     * (double) v < to; a doc without a value is in no range; overlapping, identical, from == to and from > to ranges are
+     * legal.  Every range is a bucket, empty or not, in the order of esgpu_range_buckets (sorted by from, then to).
+     * Sub-aggregations: stats, extended_stats, avg, sum, min, max, value_count over single-valued long / double
+     * fields.  Result block: n_buckets = the ranges per instance, doc_counts, subs, the keys in term_offsets / term_bytes,
+     * the bounds in range_from / range_to, keyed, value_format / format / time_zone.
+     * Refused with ESGPU_ERR_INVALID: no ranges, a NaN bound.  Refused with ESGPU_ERR_UNSUPPORTED (the plugin keeps the
+     * Java aggregator): more than 64 ranges (a doc's ranges are one u64 mask); a range that is not top level (under a
+     * filter aggregation included); a bucket, filter or cardinality sub-aggregation; a keyword or ESGPU_COL_U64 range
+     * field; a multi-valued metric field, or value_count over a keyword or multi-valued field, under a range;
+     * ESGPU_FORMAT_NUMBER on the range (its keys would need DecimalFormat); a date format other than the mapping's
+     * default (strict_date_optional_time, with or without ||epoch_millis), which is all the date printer prints.
+     * date_range, ip_range, geo_distance and string bounds (date math) are not covered. */
+    ESGPU_AGG_RANGE = 13
 };
+
+/* One range of an ESGPU_AGG_RANGE spec (RangeAggregator.Range): [from, to) on doubles; -Infinity / +Infinity = an
+ * unbounded side; key NULL = the generated key (InternalRange.Bucket.generateKey). */
+typedef struct esgpu_range {
+    const char* key;
+    double from;
+    double to;
+} esgpu_range;
 
 /* terms order (InternalOrder.java:47-76; compound with _term asc tie-break for the count orders) */
 enum {
@@ -324,6 +347,10 @@ typedef struct esgpu_agg_spec {
     int32_t value_format;
     int32_t reserved_fmt;
     const char* format;
+    /* range (RangeParser.java:44-113): the ranges in request order; `keyed` applies */
+    const esgpu_range* ranges;
+    int32_t n_ranges;
+    int32_t reserved_ranges;
 } esgpu_agg_spec;
 
 enum {
@@ -364,6 +391,14 @@ int esgpu_precision_from_threshold(int64_t count, int32_t* precision);
  * op 0 = round(value), 1 = nextRoundingValue(value), 2 = roundKey(value).  Callers use it for ExtendedBounds.round
  * (ExtendedBounds.java) before filling esgpu_agg_spec.extended_bounds_*. */
 int esgpu_date_rounding(const esgpu_agg_spec* spec, int32_t op, int64_t value, int64_t* out);
+/* The buckets of an ESGPU_AGG_RANGE spec as esgpu_plan_create makes them: order_out[b] = the index into spec->ranges of
+ * bucket b -- the ranges sorted stably by (from, to) in Double.compare order (RangeAggregator.java:96-119) -- and the
+ * buckets' keys, NUL-separated, in keys_buf (at most cap bytes; *needed = the full length).  A key is the range's own,
+ * or generateKey: "*" for an infinite side, else the formatter's text of the bound -- ESGPU_FORMAT_RAW: Double.toString
+ * ("*-50.0", "1.0E7-*"); ESGPU_FORMAT_DATE_TIME: the date printer over (long) bound in UTC
+ * ("2015-09-01T00:00:00.000Z-*").  order_out (n_ranges entries) and keys_buf may be NULL.  Refusals as for
+ * esgpu_plan_create (ESGPU_AGG_RANGE above). */
+int esgpu_range_buckets(const esgpu_agg_spec* spec, int32_t* order_out, char* keys_buf, size_t cap, size_t* needed);
 /* MurmurHash3_x64_128 (common/hash/MurmurHash3.java:62-157): the murmur3 field's index-time hash is out[0] (h1)
  * (plugins/mapper-murmur3/.../Murmur3FieldMapper.java:152-165). */
 int esgpu_murmur3_x64_128(const uint8_t* bytes, size_t len, int64_t seed, uint64_t* out2);
@@ -412,7 +447,9 @@ int esgpu_plan_destroy(esgpu_plan* plan);
  * 1 LDS grid, 2 LDS key window, 3 HLL registers, 4 partitioned terms counting, 5 multi-valued (CSR) columns, 6 hot/cold
  * terms scatter form, 7 hot/cold postings form, 8 hot slots only (cold lists deferred to the top-k), 9 hot slots of a
  * filtered request (the scatter form deferred to the top-k), 10 LDS key window over the top-ranked terms (the segment
- * is retained -- esgpu_plan_deferred_segments -- and collected again over every term if the request brings a second). */
+ * is retained -- esgpu_plan_deferred_segments -- and collected again over every term if the request brings a second),
+ * 11 the range collect (one pass over the range field and one metric field per pipeline; bytes: each column at the 8
+ * bytes read, CSR offsets, the doc bitset of a filtered request and the columns its clauses read). */
 int esgpu_plan_last_collect_stats(const esgpu_plan* plan, double* kernel_ms, uint64_t* algorithmic_bytes,
                                   int32_t* path);
 /* The kernel that ran the last collect's LDS-window launch: 0 the generic collect kernel, 1 the ranked kernel (path 10
@@ -502,6 +539,8 @@ struct esgpu_agg_block {
     int32_t terms_kind;                     /* terms: 0 = StringTerms, 1 = LongTerms (a long / date field) */
     int32_t reserved_kind;
     const int64_t* term_longs;              /* [n_buckets] terms_kind 1: the bucket keys (term_bytes holds their decimal text) */
+    const double* range_from;               /* [n_buckets] range: the buckets' bounds (+-Infinity = unbounded); keys in term_bytes */
+    const double* range_to;
 };
 
 struct esgpu_result {
@@ -535,11 +574,12 @@ int esgpu_result_to_json(const esgpu_result* r, char* buf, size_t cap, size_t* n
 int esgpu_result_to_xcontent(const esgpu_result* r, char* buf, size_t cap, size_t* needed);
 /* Elasticsearch's transport wire format of a shard result: the bytes InternalAggregations.writeTo(StreamOutput) writes
  * (InternalAggregations.java:215-222) -- per aggregation its AggregationStreams type ("sterms", "dhisto", "histo",
- * "stats", "estats", "avg", "cardinality", "filter"), InternalAggregation.writeTo (name, null metadata, no pipeline
+ * "stats", "estats", "avg", "cardinality", "filter", "range"), InternalAggregation.writeTo (name, null metadata, no pipeline
  * aggregators, InternalAggregation.java:212-221) and the class's doWriteTo (StringTerms.java:205-217 + Bucket.writeTo
  * :128-136, InternalHistogram.java:510-523 + Bucket.writeTo :183-187 + EmptyBucketInfo :223-230, InternalStats.java:
  * 182-189, InternalExtendedStats.java:169-174, InternalAvg.java:102-106, InternalCardinality.java:92-100 +
- * HyperLogLogPlusPlus.writeTo :519-535, InternalSingleBucketAggregation.java:124-127), with StreamOutput's encodings
+ * HyperLogLogPlusPlus.writeTo :519-535, InternalSingleBucketAggregation.java:124-127, InternalRange.java:323-337), with
+ * StreamOutput's encodings
  * (vInt/vLong, big-endian long/int, writeString as Java chars in modified UTF-8, StreamOutput.java:118-270).
  * A JNI shim hands these bytes to StreamInput and InternalAggregations.readAggregations to get the Java objects.
  * A LINEAR_COUNTING cardinality writes its hashes in the slot order of the reference's Hashset (HyperLogLogPlusPlus

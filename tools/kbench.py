@@ -28,7 +28,20 @@ from elasticsearch_amd import QueryBuilders as QB  # noqa: E402
 def variants():
     ns = lambda m: AB.terms("hosts").field("host").size(10).subAggregation(  # noqa: E731
         AB.dateHistogram("h").field("@timestamp").interval("1h").subAggregation(m))
+    # five latency classes over response_time_ms, each with stats(bytes): as one range aggregation (one pass over the two
+    # columns) and as its twin, five top-level filter aggregations with a gte / lt range clause and the same child
+    cuts = [None, 50, 100, 250, 500, None]
+    rng = AB.range("lat").field("response_time_ms").subAggregation(AB.stats("b").field("bytes"))
+    flt5 = []
+    for k, (lo, hi) in enumerate(zip(cuts[:-1], cuts[1:])):
+        rng.addRange(float("-inf") if lo is None else lo, float("inf") if hi is None else hi)
+        q = QB.rangeQuery("response_time_ms")
+        q = q if lo is None else q.gte(lo)
+        q = q if hi is None else q.lt(hi)
+        flt5.append(AB.filter("f%d" % k, q).subAggregation(AB.stats("b").field("bytes")))
     return {
+        "range5_stats": ([rng], None),
+        "filters5_stats": (flt5, None),
         "terms_host": ([AB.terms("hosts").field("host")], None),
         "date_hist": ([AB.dateHistogram("h").field("@timestamp").interval("1h")], None),
         "config2_dh_ext": ([AB.dateHistogram("h").field("@timestamp").interval("1h").subAggregation(
