@@ -25,7 +25,7 @@ SYNTH_TYPES = {
     "response_time_ms": COL_I64, "bytes": COL_I64, "client_ip.hash": COL_U64, "price": COL_F64,
 }
 AGG_TERMS, AGG_HISTOGRAM, AGG_DATE_HISTOGRAM, AGG_STATS, AGG_EXTENDED_STATS, AGG_AVG, AGG_CARDINALITY = 1, 2, 3, 4, 5, 6, 7
-AGG_SUM, AGG_MIN, AGG_MAX, AGG_VALUE_COUNT, AGG_FILTER, AGG_RANGE = 8, 9, 10, 11, 12, 13
+AGG_SUM, AGG_MIN, AGG_MAX, AGG_VALUE_COUNT, AGG_FILTER, AGG_RANGE, AGG_FILTERS = 8, 9, 10, 11, 12, 13, 14
 ORDER_COUNT_DESC, ORDER_COUNT_ASC, ORDER_TERM_ASC, ORDER_TERM_DESC = 0, 1, 2, 3
 ORDER_KEY_ASC, ORDER_KEY_DESC, ORDER_HCOUNT_ASC, ORDER_HCOUNT_DESC = 4, 5, 6, 7
 ORDER_AGG_ASC, ORDER_AGG_DESC = 8, 9
@@ -64,6 +64,8 @@ class AggSpec(ctypes.Structure):
         ("time_zone", ctypes.c_char_p), ("value_format", ctypes.c_int32), ("reserved_fmt", ctypes.c_int32),
         ("format", ctypes.c_char_p),
         ("ranges", ctypes.POINTER(Range)), ("n_ranges", ctypes.c_int32), ("reserved_ranges", ctypes.c_int32),
+        ("filter_keys", ctypes.POINTER(ctypes.c_char_p)), ("n_filters", ctypes.c_int32), ("other_bucket", ctypes.c_int32),
+        ("other_bucket_key", ctypes.c_char_p),
     ]
 
 
@@ -75,6 +77,7 @@ class Filter(ctypes.Structure):
         ("lo_d", ctypes.c_double), ("hi_d", ctypes.c_double),
         ("lo_term", ctypes.c_char_p), ("hi_term", ctypes.c_char_p), ("lo_term_len", ctypes.c_uint64),
         ("hi_term_len", ctypes.c_uint64),
+        ("slot", ctypes.c_int32), ("reserved_slot", ctypes.c_int32),  # the filter of a filters aggregation (owner)
     ]
 
 

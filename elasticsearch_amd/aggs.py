@@ -12,6 +12,7 @@ flattened esgpu_agg_spec array of include/esgpu.h.
 """
 import ctypes
 import functools
+import math
 import re
 
 from . import _native as N
@@ -383,9 +384,59 @@ class RangeBuilder(_Builder):
     add_unbounded_from = addUnboundedFrom
 
 
+class FiltersBuilder(_Builder):
+    """filters aggregation (FiltersAggregator / InternalFilters, FiltersAggregationBuilder): one bucket per filter, in
+    request order, a doc in every bucket whose filter it matches, and optionally the "other" bucket of the docs matching
+    none.  filter(key, query) adds a named filter (a repeated key replaces the query and keeps its position),
+    filter(query) an anonymous one (keys "0", "1", ...); a query is a TermQuery, a RangeQuery or a list of them (their
+    conjunction; the empty list is match_all).  On the GPU path at the top level with numeric metric sub-aggregations."""
+    type = N.AGG_FILTERS
+
+    def __init__(self, name):
+        super().__init__(name)
+        self._keyed_filters = {}  # key -> query, in insertion order (FiltersAggregationBuilder's LinkedHashMap)
+        self._anon_filters = []
+        self._other = False
+        self._other_key = None
+
+    def filter(self, *args):
+        if len(args) == 2:
+            self._keyed_filters[str(args[0])] = args[1]
+        elif len(args) == 1:
+            self._anon_filters.append(args[0])
+        else:
+            raise TypeError("expected filter([key,] query)")
+        return self
+
+    def otherBucket(self, other):  # noqa: N802
+        self._other = bool(other)
+        return self
+
+    def otherBucketKey(self, key):  # noqa: N802 -- FiltersParser.java:104-107: a key implies the other bucket
+        self._other_key = str(key)
+        self._other = True
+        return self
+
+    other_bucket = otherBucket
+    other_bucket_key = otherBucketKey
+
+    def filters(self):
+        """-> (keyed, [(key, [clauses])]) in bucket order; ValueError as FiltersAggregationBuilder.internalXContent
+        throws (:97-101): no filter at all, or keyed and anonymous filters mixed"""
+        if not self._keyed_filters and not self._anon_filters:
+            raise ValueError("At least one filter must be set on filter aggregation [%s]" % self.name)
+        if self._keyed_filters and self._anon_filters:
+            raise ValueError("Cannot add both keyed and non-keyed filters to filters aggregation [%s]" % self.name)
+        as_list = lambda q: list(q) if isinstance(q, (list, tuple)) else [q]  # noqa: E731
+        if self._keyed_filters:
+            return True, [(k, as_list(q)) for k, q in self._keyed_filters.items()]
+        return False, [(str(i), as_list(q)) for i, q in enumerate(self._anon_filters)]
+
+
 class AggregationBuilders:
     terms = TermsBuilder
     filter = FilterBuilder
+    filters = FiltersBuilder
     range = RangeBuilder
     histogram = HistogramBuilder
     dateHistogram = DateHistogramBuilder
@@ -579,6 +630,15 @@ def flatten(aggs, number_of_shards=1):
             keep.append(rs)
             sp.ranges = ctypes.cast(rs, ctypes.POINTER(N.Range))
             sp.n_ranges = len(b._ranges)
+        elif b.type == N.AGG_FILTERS:
+            keyed, flt = b.filters()
+            sp.keyed = int(keyed)
+            ks = (ctypes.c_char_p * len(flt))(*[enc(k) for k, _q in flt])
+            keep.append(ks)
+            sp.filter_keys = ctypes.cast(ks, ctypes.POINTER(ctypes.c_char_p))
+            sp.n_filters = len(flt)
+            sp.other_bucket = int(b._other)
+            sp.other_bucket_key = enc(b._other_key)
         elif b.type == N.AGG_EXTENDED_STATS:
             sp.sigma = b._sigma
         elif b.type == N.AGG_CARDINALITY:
@@ -608,17 +668,29 @@ def _preorder(aggs):
     return [(b, i) for i, b in enumerate(out)]
 
 
+def _bound_i64(v):
+    """lo_i / hi_i of a range bound.  An infinite bound travels in lo_d / hi_d, which every column type reads for it
+    (include/esgpu.h); the long beside it only has to fit the field.  A NaN bound raises, as int() does."""
+    if isinstance(v, float) and math.isinf(v):
+        return (1 << 63) - 1 if v > 0 else -(1 << 63)
+    return int(v)
+
+
 def flatten_filters(queries, ord_lookup=None, aggs=None):
     """Queries -> ctypes array of Filter.  `ord_lookup(field, term) -> ordinal or -1` resolves keyword terms.  With
-    `aggs`, the clauses of every filter aggregation follow, each tagged with its owner (spec index + 1)."""
+    `aggs`, the clauses of every filter aggregation follow, each tagged with its owner (spec index + 1), and those of
+    every filters aggregation, tagged with the owner and the slot of their filter."""
     out, keep = [], []
-    tagged = [(q, 0) for q in queries or []]
+    tagged = [(q, 0, 0) for q in queries or []]
     for b, i in _preorder(aggs):
         if b.type == N.AGG_FILTER:
-            tagged += [(q, i + 1) for q in b.clauses()]
-    for q, owner in tagged:
+            tagged += [(q, i + 1, 0) for q in b.clauses()]
+        elif b.type == N.AGG_FILTERS:
+            tagged += [(q, i + 1, slot) for slot, (_key, qs) in enumerate(b.filters()[1]) for q in qs]
+    for q, owner, slot in tagged:
         f = N.Filter()
         f.owner = owner
+        f.slot = slot
         b = q.field.encode("utf-8")
         keep.append(b)
         f.field = b
@@ -639,7 +711,7 @@ def flatten_filters(queries, ord_lookup=None, aggs=None):
                     keep.append(b)
                     f.lo_term, f.lo_term_len = b, len(b)
                 else:
-                    f.lo_i, f.lo_d = int(q.lo), float(q.lo)
+                    f.lo_i, f.lo_d = _bound_i64(q.lo), float(q.lo)
             if q.hi is not None:
                 f.has_upper, f.include_upper = 1, int(q.include_upper)
                 if isinstance(q.hi, (str, bytes)):
@@ -647,7 +719,7 @@ def flatten_filters(queries, ord_lookup=None, aggs=None):
                     keep.append(b)
                     f.hi_term, f.hi_term_len = b, len(b)
                 else:
-                    f.hi_i, f.hi_d = int(q.hi), float(q.hi)
+                    f.hi_i, f.hi_d = _bound_i64(q.hi), float(q.hi)
         out.append(f)
     arr = (N.Filter * max(len(out), 1))(*out)
     return arr, len(out), keep

@@ -215,6 +215,45 @@ struct RangeParams {
 void launch_range(const RangeParams& p, int met, uint32_t grid, hipStream_t s);
 int range_occupancy(int met, bool multi);
 
+// The filters collect (esgpu_filters.hip, path 12): one pass over the distinct clause columns of a filters aggregation
+// and one metric field into the [R] cells of a pipeline's ordinary grid (T = R buckets: the filters, then the other
+// bucket; H = 1).  Per clause column the host cuts the key line at the clauses' bounds (es_filter_masks.hpp): `table`
+// holds kFilterStride u64 per column -- [kRangeCuts] cuts ascending, [kRangeCuts + 1] masks (bit i: every clause of
+// filter i on the column accepts the interval), then the mask of a doc without a value there.  A doc's mask is the AND
+// over the columns (all_mask with no column: every filter is match_all).
+constexpr uint32_t kFilterCols = 4;                       // distinct clause columns per aggregation
+constexpr uint32_t kFilterStride = 2 * kRangeCuts + 2;
+enum FilterColKind : int32_t { FCOL_ORD = 0, FCOL_I64 = 1, FCOL_F64 = 2 };
+struct FilterCol {
+    const void* v;             // single-valued, per doc: u32 ordinals (FCOL_ORD) or 8 bytes
+    const uint64_t* present;   // null = dense (ordinal columns mark a missing value by kMissingOrd)
+    int32_t kind;
+    uint32_t n_cuts;
+};
+struct FiltersParams {
+    FilterCol col[kFilterCols];
+    uint32_t n_cols;
+    uint32_t R;                  // buckets, the other bucket included
+    int32_t other_bit;           // the other bucket's bit (= the number of filters); -1 = none
+    int32_t mv_f64, vcnt_mode;
+    uint32_t n_docs, n_blocks, blocks_per_wg;
+    uint64_t all_mask;           // the filters' bits
+    const void* mv;              // the metric field's values, single-valued, 8 bytes per doc (null: counts only)
+    const uint64_t* mv_present;
+    const uint64_t* accept;      // doc bitset: accept bits and every query clause folded (launch_filter_bits); null = all docs
+    const uint64_t* table;       // device: [n_cols][kFilterStride]
+    unsigned long long* g_cnt;
+    unsigned long long* g_vcnt;
+    double* g_sum;
+    unsigned long long* g_min;
+    unsigned long long* g_max;
+    double* g_sq;
+    double* g_sum_lo;
+    double* g_sq_lo;
+};
+void launch_filters(const FiltersParams& p, int met, uint32_t grid, hipStream_t s);
+int filters_occupancy(int met);
+
 enum HllKind : int32_t { HLL_I64 = 0, HLL_F64 = 1, HLL_ORD = 2 };
 
 struct HllParams {

@@ -8,60 +8,26 @@
 // a long column against long cuts (the host made each the least long whose double reaches the bound), a double column
 // through the order-preserving image of its bits (rg_key; NaN and +Infinity belong to no range).
 //
-// Accumulation: a thread holds 8 docs (masks and metric values) in registers; for every range present in the wave the
-// wave reduces first -- ballots for the counts, wave_sum_f64 / wave_min_u64 / wave_max_u64 for the metric -- and lane 0
-// updates the workgroup's LDS cell of that range once.  The cells reach the grid in one flush per workgroup, one atomic
-// per non-empty cell and array (compensated where the pipeline's double-double rule is on).  No global atomic and no
-// LDS atomic per doc.
-#include "esgpu_collect.hpp"
+// Accumulation and flush: esgpu_range_cells.hpp (shared with the filters collect).
+#include "esgpu_range_cells.hpp"
 
 namespace esgpu {
-
-constexpr int kRgWG = 256;
-constexpr uint32_t kRgQuad = kRgWG * 4;        // docs of one 16-byte-per-lane sweep of the workgroup (two loads per column)
-constexpr uint32_t kRgQuads = 2;               // sweeps per reduction round
-constexpr uint32_t kRgDocs = 4 * kRgQuads;     // docs per thread per round
-constexpr uint32_t kRgRound = kRgQuad * kRgQuads;
-static_assert(kBlockDocs % kRgRound == 0, "a zone block is a whole number of rounds");
 
 struct RgLds {
     long long cuts[kRangeCuts];
     unsigned long long masks[kRangeCuts + 1];
-    unsigned long long cnt[kRangeMax], vcnt[kRangeMax];
-    double sum[kRangeMax];
-    unsigned long long mn[kRangeMax], mx[kRangeMax];
-    double sq[kRangeMax];
+    RgCells cells;
 };
 
-// the signed key doubles compare by (-0.0 just below +0.0: the host's cut for a bound of 0.0 is the key of -0.0)
-__device__ __forceinline__ long long rg_key(unsigned long long bits) {
-    const long long b = (long long)bits;
-    return b ^ ((b >> 63) & 0x7FFFFFFFFFFFFFFFll);
-}
-
-// mask of a value: masks[k], k = the number of cuts <= key (the largest k in [0, n] with cuts[k - 1] <= key)
-__device__ __forceinline__ unsigned long long rg_lookup(const RgLds& S, uint32_t n, uint32_t step0, long long key) {
-    uint32_t k = 0;
-    for (uint32_t step = step0; step; step >>= 1) {
-        const uint32_t t = k + step;
-        if (t <= n && S.cuts[t - 1] <= key) k = t;
-    }
-    return S.masks[k];
-}
+// a value's mask (rg_key puts -0.0 just below +0.0: the host's cut for a bound of 0.0 is the key of -0.0)
 template <bool F64>
 __device__ __forceinline__ unsigned long long rg_value_mask(const RgLds& S, uint32_t n, uint32_t step0, unsigned long long bits) {
     if (F64) {
         const double d = bits_dbl(bits);
         if (!(d < INFINITY)) return 0ull;  // NaN >= from and +Infinity < to are false for every range
-        return rg_lookup(S, n, step0, rg_key(bits));
+        return rg_lookup(S.cuts, S.masks, n, step0, rg_key(bits));
     }
-    return rg_lookup(S, n, step0, (long long)bits);
-}
-
-__device__ __forceinline__ unsigned long long wave_or_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
-    return v;
+    return rg_lookup(S.cuts, S.masks, n, step0, (long long)bits);
 }
 
 template <int MET, bool MULTI>
@@ -70,14 +36,7 @@ __global__ __launch_bounds__(kRgWG) void range_kernel(RangeParams P) {
     const uint32_t n = P.n_cuts, R = P.R;
     for (uint32_t i = threadIdx.x; i < n; i += kRgWG) S.cuts[i] = (long long)P.table[i];
     for (uint32_t i = threadIdx.x; i <= n; i += kRgWG) S.masks[i] = P.table[kRangeCuts + i];
-    for (uint32_t i = threadIdx.x; i < kRangeMax; i += kRgWG) {
-        S.cnt[i] = 0;
-        S.vcnt[i] = 0;
-        S.sum[i] = 0.0;
-        S.mn[i] = kMinInit;
-        S.mx[i] = kMaxInit;
-        S.sq[i] = 0.0;
-    }
+    rg_cells_init(S.cells);
     __syncthreads();
     uint32_t step0 = 0;
     if (n) step0 = 1u << (31 - __clz((int)n));
@@ -139,77 +98,10 @@ __global__ __launch_bounds__(kRgWG) void range_kernel(RangeParams P) {
                 }
             }
         }
-        unsigned long long any = 0ull;
-#pragma unroll
-        for (uint32_t j = 0; j < kRgDocs; ++j) any |= m[j];
-        any = wave_or_u64(any);
-        uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)any), hi = __builtin_amdgcn_readfirstlane((uint32_t)(any >> 32));
-        // one pass per range present in the wave (uniform)
-        while (lo | hi) {
-            uint32_t r;
-            if (lo) { r = __builtin_ctz(lo); lo &= lo - 1u; }
-            else { r = 32u + __builtin_ctz(hi); hi &= hi - 1u; }
-            uint32_t c = 0, vc = 0;
-            double s = 0.0, sq = 0.0;
-            unsigned long long mn = kMinInit, mx = kMaxInit;
-#pragma unroll
-            for (uint32_t j = 0; j < kRgDocs; ++j) {
-                const bool in = (m[j] >> r) & 1ull;
-                c += __popcll(__ballot(in));
-                if constexpr (MET > 0) {
-                    const bool has = in && ((mp >> j) & 1u);
-                    if (vcnt) vc += __popcll(__ballot(has));
-                    s += has ? x[j] : 0.0;
-                    if constexpr (MET >= 2) {
-                        const bool nan = x[j] != x[j];
-                        const unsigned long long e = sortable(x[j]);
-                        const unsigned long long emn = nan ? 0ull : e, emx = nan ? ~0ull : e;
-                        if (has && emn < mn) mn = emn;
-                        if (has && emx > mx) mx = emx;
-                    }
-                    if constexpr (MET >= 3) sq += has ? x[j] * x[j] : 0.0;  // (sumOfSqr += value * value, no FMA)
-                }
-            }
-            if constexpr (MET > 0) {
-                s = wave_sum_f64(s);
-                if constexpr (MET >= 2) {
-                    mn = wave_min_u64(mn);
-                    mx = wave_max_u64(mx);
-                }
-                if constexpr (MET >= 3) sq = wave_sum_f64(sq);
-            }
-            if (lane0) {
-                atomicAdd(&S.cnt[r], (unsigned long long)c);
-                if constexpr (MET > 0) {
-                    if (vcnt) atomicAdd(&S.vcnt[r], (unsigned long long)vc);
-                    atomicAdd(&S.sum[r], s);
-                    if constexpr (MET >= 2) {
-                        atomicMin(&S.mn[r], mn);
-                        atomicMax(&S.mx[r], mx);
-                    }
-                    if constexpr (MET >= 3) atomicAdd(&S.sq[r], sq);
-                }
-            }
-        }
+        rg_accumulate<MET>(S.cells, m, x, mp, vcnt, lane0);
     }
     __syncthreads();
-    // the workgroup's cells into the grid: one atomic per non-empty cell and array
-    const uint32_t r = threadIdx.x;
-    if (r < R && S.cnt[r] != 0) {
-        atomicAdd(&P.g_cnt[r], S.cnt[r]);
-        if constexpr (MET > 0) {
-            const bool some = !vcnt || S.vcnt[r] != 0;  // (docs of the range, none with a metric value: nothing to add)
-            if (vcnt && some) atomicAdd(&P.g_vcnt[r], S.vcnt[r]);
-            if (some) {
-                dd_atomic_add(&P.g_sum[r], P.g_sum_lo ? P.g_sum_lo + r : nullptr, S.sum[r]);
-                if constexpr (MET >= 2) {
-                    if (S.mn[r] != kMinInit) atomicMin(&P.g_min[r], S.mn[r]);
-                    if (S.mx[r] != kMaxInit) atomicMax(&P.g_max[r], S.mx[r]);
-                }
-                if constexpr (MET >= 3) dd_atomic_add(&P.g_sq[r], P.g_sq_lo ? P.g_sq_lo + r : nullptr, S.sq[r]);
-            }
-        }
-    }
+    rg_flush<MET>(S.cells, P, R, vcnt);
 }
 
 template <int MET>

@@ -987,7 +987,11 @@ void reduce_level(const Level& lv, Block& out) {
             if (!fused_leaf(out.subs[j])) reduce_level(child[j], out.subs[j]);
         return;
     }
-    if (out.is_range()) {  // InternalRange.doReduce (:290-311): by position -- doc counts add, the buckets' subs reduce
+    if (out.is_range() || out.is_filters()) {
+        // InternalRange.doReduce (:290-311), InternalFilters.doReduce (:204-228): by position -- doc counts add, the
+        // buckets' subs reduce
+        const bool rng = out.is_range();
+        const char* what = rng ? "range" : "filters";
         std::vector<Level> child(out.subs.size());
         std::vector<Ref> rs;
         for (const Group& g : lv.groups) {
@@ -998,7 +1002,8 @@ void reduce_level(const Level& lv, Block& out) {
             for (size_t x = 1; x < n; ++x) {
                 const Block& s = *refs[x].b;
                 if (s.boff[refs[x].i + 1] - s.boff[refs[x].i] != R)
-                    throw std::invalid_argument("range aggregation [" + out.name + "]: shards carry different numbers of ranges");
+                    throw std::invalid_argument(std::string(what) + " aggregation [" + out.name +
+                                                "]: shards carry different numbers of " + (rng ? "ranges" : "buckets"));
             }
             ++out.n;
             out.doc_count_error.push_back(0);
@@ -1009,8 +1014,10 @@ void reduce_level(const Level& lv, Block& out) {
                 out.key.push_back((int64_t)k);
                 out.term_pool.append(f.term_pool, f.term_off[f0 + k], f.term_off[f0 + k + 1] - f.term_off[f0 + k]);
                 out.term_off.push_back(out.term_pool.size());
-                out.rfrom.push_back(f.rfrom[f0 + k]);
-                out.rto.push_back(f.rto[f0 + k]);
+                if (rng) {
+                    out.rfrom.push_back(f.rfrom[f0 + k]);
+                    out.rto.push_back(f.rto[f0 + k]);
+                }
                 out.bcount.push_back(dc);
                 out.berr.push_back(0);
                 for (size_t j = 0; j < out.subs.size(); ++j) {
@@ -1308,6 +1315,18 @@ void write_instance(J& j, const Block& a, uint64_t i) {
             }
             j.raw("]");
             break;
+        case ESGPU_AGG_FILTERS:  // every bucket in result order, each with its key (the anonymous form's: "0", "1", ...)
+            j.key("buckets"); j.raw("[");
+            for (uint64_t k = a.boff[i]; k < a.boff[i + 1]; ++k) {
+                if (k != a.boff[i]) j.raw(",");
+                j.raw("{"); j.key("key");
+                j.str(a.term_pool.data() + a.term_off[k], a.term_off[k + 1] - a.term_off[k]);
+                j.raw(","); j.key("doc_count"); j.i64(a.bcount[k]);
+                write_subs(j, a, k);
+                j.raw("}");
+            }
+            j.raw("]");
+            break;
         case ESGPU_AGG_AVG:
             j.key("value"); j.opt(a.count[i] != 0, a.sum[i] / (double)a.count[i]);
             j.raw(","); j.key("_internal"); j.raw("{"); j.key("count"); j.i64(a.count[i]); j.raw(",");
@@ -1538,6 +1557,18 @@ void x_instance(X& x, const Block& a, uint64_t i) {
             }
             x.raw(a.keyed ? "}" : "]");
             break;
+        case ESGPU_AGG_FILTERS:  // InternalFilters.doXContentBody (:254-268), Bucket.toXContent (:133-143)
+            x.key("buckets"); x.raw(a.keyed ? "{" : "[");
+            for (uint64_t k = a.boff[i]; k < a.boff[i + 1]; ++k) {
+                if (k != a.boff[i]) x.raw(",");
+                if (a.keyed) x.key(a.term(k));
+                x.raw("{");
+                x.key("doc_count"); x.i64(a.bcount[k]);
+                x_subs(x, a, k);
+                x.raw("}");
+            }
+            x.raw(a.keyed ? "}" : "]");
+            break;
         case ESGPU_AGG_AVG:
             x.key("value"); x.opt(a.count[i] != 0, a.sum[i] / (double)a.count[i]);
             break;
@@ -1626,6 +1657,20 @@ std::vector<RangeBucket> range_buckets(const esgpu_agg_spec& spec) {
     return out;
 }
 
+std::vector<std::string> filters_bucket_keys(const esgpu_agg_spec& spec) {
+    if (spec.n_filters <= 0) throw std::invalid_argument("[filters] aggregation requires at least one filter");
+    if (spec.keyed && !spec.filter_keys) throw std::invalid_argument("a named [filters] aggregation without its keys");
+    if ((int64_t)spec.n_filters + (spec.other_bucket ? 1 : 0) > 64)
+        throw std::domain_error("a filters aggregation over more than 64 buckets runs on the CPU path");
+    std::vector<std::string> keys;
+    for (int32_t i = 0; i < spec.n_filters; ++i) {
+        if (spec.keyed && !spec.filter_keys[i]) throw std::invalid_argument("a named [filters] aggregation with a null key");
+        keys.push_back(spec.keyed ? std::string(spec.filter_keys[i]) : std::to_string(i));
+    }
+    if (spec.other_bucket) keys.push_back(spec.other_bucket_key ? spec.other_bucket_key : "_other_");
+    return keys;
+}
+
 std::string to_xcontent(const std::vector<Block>& aggs) {
     X x;
     x.raw("{");
@@ -1710,6 +1755,7 @@ const char* stream_type(int32_t type) {  // InternalAggregation.Type stream name
         case ESGPU_AGG_CARDINALITY: return "cardinality";    // InternalCardinality.java:39
         case ESGPU_AGG_FILTER: return "filter";              // InternalFilter.java:36
         case ESGPU_AGG_RANGE: return "range";                // InternalRange.java:44
+        case ESGPU_AGG_FILTERS: return "filters";            // InternalFilters.java:45
     }
     throw std::invalid_argument("aggregation type without a stream");
 }
@@ -1896,6 +1942,18 @@ void es_instance(JavaOut& w, const Block& a, uint64_t i) {
             }
             break;
         }
+        case ESGPU_AGG_FILTERS: {  // InternalFilters.doWriteTo (:245-251), Bucket.writeTo (:153-157)
+            w.boolean(a.keyed != 0);
+            const uint64_t b0 = a.boff[i], b1 = a.boff[i + 1];
+            w.vint((int32_t)(b1 - b0));
+            for (uint64_t b = b0; b < b1; ++b) {
+                w.boolean(true);  // writeOptionalString: a bucket always has its key (the anonymous form's: its index)
+                w.str(a.term(b));
+                w.vlong(a.bcount[b]);
+                es_list(w, a.subs, b);
+            }
+            break;
+        }
         default: throw std::invalid_argument("aggregation type without a stream");
     }
 }
@@ -2012,7 +2070,8 @@ void r_block(R& r, Block& a, int depth) {
     const bool bucket = a.has_buckets();
     if (a.rfrom.size() != (a.is_range() ? a.nbuckets() : 0) || a.rto.size() != a.rfrom.size())
         throw std::runtime_error("inconsistent range bounds");
-    if (a.is_range() && !a.empty_subs.empty()) throw std::runtime_error("empty-bucket prototypes on a range block");
+    if ((a.is_range() || a.is_filters()) && !a.empty_subs.empty())
+        throw std::runtime_error("empty-bucket prototypes on a range or filters block");
     if (!bucket && (a.terms_kind != 0 || !a.term_long.empty())) throw std::runtime_error("long terms fields on a block without buckets");
     if (bucket) {
         const uint64_t nb = a.boff.empty() ? 0 : a.boff.back();
@@ -2066,7 +2125,14 @@ void r_blocks(R& r, std::vector<Block>& l, int depth) {
 const uint32_t kStreamMagic = 0x45534750;  // "ESGP"
 // version 6 = version 5 plus, per block, the terms kind and the long keys; written only when a result holds LongTerms
 // version 7 = version 6 plus, per block, the range bounds; written only when a result holds a range block
-const uint32_t kStreamVersion = 5, kStreamVersionLongTerms = 6, kStreamVersionRange = 7;
+// version 8 = the layout of version 7; written only when a result holds a filters block, whose type a reader of
+// versions 5 to 7 does not know (it refuses the record by its version)
+const uint32_t kStreamVersion = 5, kStreamVersionLongTerms = 6, kStreamVersionRange = 7, kStreamVersionFilters = 8;
+bool has_filters(const std::vector<Block>& l) {
+    for (const Block& a : l)
+        if (a.is_filters() || has_filters(a.subs) || has_filters(a.empty_subs)) return true;
+    return false;
+}
 bool has_range(const std::vector<Block>& l) {
     for (const Block& a : l)
         if (a.is_range() || has_range(a.subs) || has_range(a.empty_subs)) return true;
@@ -2082,7 +2148,10 @@ bool has_long_terms(const std::vector<Block>& l) {
 void serialize(const std::vector<Block>& aggs, std::string& out) {
     out.clear();
     W w{out};
-    w.version = has_range(aggs) ? kStreamVersionRange : has_long_terms(aggs) ? kStreamVersionLongTerms : kStreamVersion;
+    w.version = has_filters(aggs)      ? kStreamVersionFilters
+                : has_range(aggs)      ? kStreamVersionRange
+                : has_long_terms(aggs) ? kStreamVersionLongTerms
+                                       : kStreamVersion;
     w.pod(kStreamMagic);
     w.pod(w.version);
     w_blocks(w, aggs);
@@ -2092,7 +2161,7 @@ bool deserialize(const uint8_t* p, size_t n, std::vector<Block>& out) {
     R r{p, n};
     if (n < 8 || r.pod<uint32_t>() != kStreamMagic) return false;
     r.version = r.pod<uint32_t>();
-    if (r.version != kStreamVersion && r.version != kStreamVersionLongTerms && r.version != kStreamVersionRange) return false;
+    if (r.version < kStreamVersion || r.version > kStreamVersionFilters) return false;
     r_blocks(r, out, 0);
     for (const Block& b : out) if (b.n != 1) throw std::runtime_error("top-level aggregations carry one instance");
     return true;

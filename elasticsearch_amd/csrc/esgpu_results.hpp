@@ -77,7 +77,10 @@ struct Block {
     // range (InternalRange): buckets in the flat arrays like the bucket aggregations above, every instance with all the
     // request's ranges; reduced by position, so it is kept apart from is_bucket()'s key-merging reduces
     bool is_range() const { return type == ESGPU_AGG_RANGE; }
-    bool has_buckets() const { return is_bucket() || is_range(); }
+    // filters (InternalFilters): like a range block without bounds -- every instance with all the request's buckets (the
+    // filters in request order, then the other bucket), their keys in term_pool, reduced by position
+    bool is_filters() const { return type == ESGPU_AGG_FILTERS; }
+    bool has_buckets() const { return is_bucket() || is_range() || is_filters(); }
     uint64_t nbuckets() const { return boff.empty() ? 0 : boff.back(); }
     // terms_kind 1: bucket b's key.  A StringTerms block met where LongTerms are reduced (a field mapped as keyword on
     // one shard and as long on another, or an old result) fails the reduce like every other mismatch of the trees.
@@ -114,6 +117,12 @@ struct RangeBucket {
 std::vector<RangeBucket> range_buckets(const esgpu_agg_spec& spec);
 // ValueFormatter.format(bound) of a range block (from_as_string / to_as_string)
 std::string range_bound_string(int32_t value_format, double v);
+
+// The bucket keys of a filters spec in result order (FiltersParser.java:60-113, FiltersAggregator.java:113-129): the
+// filters' keys -- `keyed`: spec.filter_keys; the anonymous form: "0", "1", ... -- then, with spec.other_bucket, the other
+// bucket's (other_bucket_key, "_other_" when null).  Throws std::invalid_argument for no filter (or a named form without
+// its keys), std::domain_error for more than 64 buckets, the other bucket included (they stay on the CPU path).
+std::vector<std::string> filters_bucket_keys(const esgpu_agg_spec& spec);
 
 // sum / min / max / value_count: single-value numeric metrics whose block fills one of the stats arrays (sum -> sum,
 // min -> min, max -> max, value_count -> count)

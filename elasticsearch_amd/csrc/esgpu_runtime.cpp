@@ -38,6 +38,7 @@
 #include "es_common.hpp"
 #include "es_rounding.hpp"
 #include "es_term_rank.hpp"
+#include "es_filter_masks.hpp"
 #include "esgpu_kernels.hpp"
 #include "esgpu_results.hpp"
 #include "esgpu_internal.hpp"
@@ -1002,6 +1003,9 @@ struct SpecNode {
     std::vector<int64_t> tz_starts, tz_offs;  // owned copy of the spec's time zone table
     std::string time_zone = "UTC", format;    // wire-stream parameters (esgpu_agg_spec.time_zone / format)
     std::vector<RangeBucket> rbuckets;        // range: its buckets in result order (range_buckets)
+    std::vector<std::string> fkeys;           // filters: its buckets' keys in result order (filters_bucket_keys)
+    int n_filters = 0;                        // filters: the filters (bits 0 .. n_filters - 1 of a doc's mask)
+    bool other_bucket = false;                // filters: bucket n_filters takes the docs matching no filter
     Rounding rounding() const {               // histogram specs (Rounding.java / TimeZoneRounding.java)
         esgpu_agg_spec sp = s;
         sp.tz_count = (int32_t)tz_starts.size();
@@ -1048,6 +1052,12 @@ struct Pipeline {
     std::string range_field;
     DevBuf d_rtable;
     int rtable_kind = 0;
+    // a filters aggregation's pipeline (collect path 12): the grid is [1][R] cells, one per bucket, filled by
+    // filters_kernel from the distinct clause columns and the pipeline's metric field; ftable: the mask tables of the
+    // clause columns (FiltersParams.table) as last uploaded -- keyword clauses resolve per segment
+    bool filters = false;
+    DevBuf d_ftable;
+    std::vector<uint64_t> ftable;
     // cell grid shape
     int outer = -1, inner = -1;      // bucket spec indices (inner may be -1)
     int term_spec = -1, hist_spec = -1;
@@ -1316,6 +1326,10 @@ static int add_pipeline(esgpu_plan* p, int root, int fspec, int outer, int inner
             pl.range_field = n.field;
             continue;
         }
+        if (n.s.type == ESGPU_AGG_FILTERS) {  // (top level, metric leaves only: no inner dimension)
+            pl.filters = true;
+            continue;
+        }
         if (n.s.type == ESGPU_AGG_TERMS && b == inner && outer >= 0 && p->specs[outer].s.type == ESGPU_AGG_TERMS) {
             // terms under terms: the inner field's ordinals are the key dimension (key = ordinal)
             pl.hist_spec = b;
@@ -1369,8 +1383,8 @@ static int add_pipeline(esgpu_plan* p, int root, int fspec, int outer, int inner
         pl.met = std::max(pl.met, metric_level(n.s.type));
         pl.sums = pl.sums || metric_has_sum(n.s.type);
     }
-    if (pl.range && pl.met == 0 && !pl.metric_field.empty()) {
-        pl.met = 1;  // value_count leaves alone under a range: counted as the field's values are streamed (no product)
+    if ((pl.range || pl.filters) && pl.met == 0 && !pl.metric_field.empty()) {
+        pl.met = 1;  // value_count leaves alone under a range or a filters aggregation: counted as the field's values are streamed (no product)
     } else if (pl.met == 0 && !pl.metric_field.empty()) {  // value_count leaves only (the product's sums are read)
         pl.vc_only = true;
         pl.sums = true;
@@ -1434,8 +1448,8 @@ static Group compile_group(esgpu_plan* p, int r, int fspec) {
         g.pipes.push_back(add_pipeline(p, r, fspec, -1, -1, {r}));
         return g;
     }
-    if (root.s.type == ESGPU_AGG_RANGE) {
-        // RangeAggregator: its metric children grouped by field, one pipeline (one pass over the range field and that
+    if (root.s.type == ESGPU_AGG_RANGE || root.s.type == ESGPU_AGG_FILTERS) {
+        // RangeAggregator / FiltersAggregator: its metric children grouped by field, one pipeline (one pass over the range field and that
         // metric field) each; every pipeline counts the ranges' docs alike and pipes[0]'s counts are the doc counts.  A
         // range without children gets one counting pipeline.
         std::vector<LeafRef> refs;
@@ -1580,7 +1594,7 @@ extern "C" int esgpu_plan_create(esgpu_ctx* c, const esgpu_agg_spec* specs, int3
             }
             n.s.time_zone = nullptr;
             n.s.format = nullptr;
-            require(n.s.type >= ESGPU_AGG_TERMS && n.s.type <= ESGPU_AGG_RANGE, ESGPU_ERR_INVALID, "unknown aggregation type");
+            require(n.s.type >= ESGPU_AGG_TERMS && n.s.type <= ESGPU_AGG_FILTERS, ESGPU_ERR_INVALID, "unknown aggregation type");
             if (n.s.type == ESGPU_AGG_RANGE) {
                 try {
                     n.rbuckets = range_buckets(specs[i]);
@@ -1593,6 +1607,21 @@ extern "C" int esgpu_plan_create(esgpu_ctx* c, const esgpu_agg_spec* specs, int3
                         "a range aggregation below the top level runs on the CPU path [" + n.name + "]");
             }
             n.s.ranges = nullptr;
+            if (n.s.type == ESGPU_AGG_FILTERS) {
+                try {
+                    n.fkeys = filters_bucket_keys(specs[i]);
+                } catch (const std::domain_error& e) {
+                    throw EsError(ESGPU_ERR_UNSUPPORTED, std::string(e.what()) + " [" + n.name + "]");
+                } catch (const std::invalid_argument& e) {
+                    throw EsError(ESGPU_ERR_INVALID, std::string(e.what()) + " [" + n.name + "]");
+                }
+                n.n_filters = n.s.n_filters;
+                n.other_bucket = n.s.other_bucket != 0;
+                require(n.s.parent < 0, ESGPU_ERR_UNSUPPORTED,
+                        "a filters aggregation below the top level runs on the CPU path [" + n.name + "]");
+            }
+            n.s.filter_keys = nullptr;
+            n.s.other_bucket_key = nullptr;
             if (n.s.type == ESGPU_AGG_FILTER && n.s.parent >= 0) {
                 // a chain of filter aggregations from the top (each one's docs: its clauses and its ancestors'), or a
                 // filter directly under a bucket aggregation of the first bucket level (compile_group)
@@ -1606,8 +1635,10 @@ extern "C" int esgpu_plan_create(esgpu_ctx* c, const esgpu_agg_spec* specs, int3
             else {
                 require(n.s.parent < i, ESGPU_ERR_INVALID, "parent must precede child");
                 const int pt = p->specs[n.s.parent].s.type;
-                require(is_bucket(pt) || pt == ESGPU_AGG_FILTER || pt == ESGPU_AGG_RANGE, ESGPU_ERR_INVALID,
+                require(is_bucket(pt) || pt == ESGPU_AGG_FILTER || pt == ESGPU_AGG_RANGE || pt == ESGPU_AGG_FILTERS, ESGPU_ERR_INVALID,
                         "metrics aggregations cannot have sub-aggregations");
+                require(pt != ESGPU_AGG_FILTERS || is_metric(n.s.type), ESGPU_ERR_UNSUPPORTED,
+                        "a filters aggregation with a bucket, filter or cardinality sub-aggregation runs on the CPU path");
                 require(pt != ESGPU_AGG_RANGE || is_metric(n.s.type), ESGPU_ERR_UNSUPPORTED,
                         "a range aggregation with a bucket, filter or cardinality sub-aggregation runs on the CPU path");
                 p->specs[n.s.parent].children.push_back(i);
@@ -1638,8 +1669,12 @@ extern "C" int esgpu_plan_create(esgpu_ctx* c, const esgpu_agg_spec* specs, int3
         for (int k = 0; k < nfilters; ++k) {
             require(filters[k].field != nullptr, ESGPU_ERR_INVALID, "filter without field");
             const int owner = filters[k].owner - 1;  // 0 = query clause, k + 1 = clause of filter aggregation spec k
-            require(owner >= -1 && owner < nspecs && (owner < 0 || p->specs[owner].s.type == ESGPU_AGG_FILTER), ESGPU_ERR_INVALID,
-                    "filter clause owner is not a filter aggregation");
+            require(owner >= -1 && owner < nspecs &&
+                        (owner < 0 || p->specs[owner].s.type == ESGPU_AGG_FILTER || p->specs[owner].s.type == ESGPU_AGG_FILTERS),
+                    ESGPU_ERR_INVALID, "filter clause owner is not a filter aggregation");
+            if (owner >= 0 && p->specs[owner].s.type == ESGPU_AGG_FILTERS)
+                require(filters[k].slot >= 0 && filters[k].slot < p->specs[owner].n_filters, ESGPU_ERR_INVALID,
+                        "filter clause slot is not a filter of its filters aggregation");
             p->filters.push_back(filters[k]);
             p->filter_fields.push_back(filters[k].field);
             p->filter_owner.push_back(owner);
@@ -1927,6 +1962,16 @@ static int b24_mode();
 static const void* wide_i64(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
 static void sampled_hot_ords(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, uint32_t (&out)[4]);
 
+// a TermRangeQuery clause over a keyword column as the ordinal range of the segment's dictionary (fm_ord_range)
+static KeyInterval ord_range_interval(const DevColumn* col, const esgpu_filter& f) {
+    if (f.has_lower) require(f.lo_term || f.lo_term_len == 0, ESGPU_ERR_INVALID, "keyword range without lower term bytes");
+    if (f.has_upper) require(f.hi_term || f.hi_term_len == 0, ESGPU_ERR_INVALID, "keyword range without upper term bytes");
+    return fm_ord_range(f, col->ord_count(), [&](const uint8_t* t, uint64_t len, uint64_t ord, bool strict) {
+        const std::string key((const char*)t, (size_t)len), m = col->ord_term(ord);
+        return strict ? m < key : !(key < m);
+    });
+}
+
 // The pipeline's clauses as device predicates: up to kMaxPreds of them are evaluated inside the collect kernels; with
 // more, all of them (and the accept bitset) are folded first into one doc bitset -- chained filter_bits passes of four
 // clauses each -- which replaces *accept, and no predicate is left for the kernel.
@@ -1947,61 +1992,26 @@ static void set_preds(esgpu_plan* p, const Pipeline& pl, const esgpu_segment* s,
             if (f.type == ESGPU_FILTER_TERM) {
                 q.kind = PRED_ORD_EQ;
                 q.lo = q.hi = f.term;
-            } else {  // TermRangeQuery: the dictionary is sorted by unsigned bytes, so the range is an ordinal range
+            } else {  // TermRangeQuery: an ordinal range of the segment's dictionary
                 q.kind = PRED_ORD_RANGE;
-                const uint64_t n = col->ord_count();
-                auto bound = [&](const uint8_t* t, uint64_t len, bool upper) {  // first ord with term > t (upper) / >= t
-                    const std::string key((const char*)t, (size_t)len);
-                    uint64_t lo = 0, hi = n;
-                    while (lo < hi) {
-                        const uint64_t mid = (lo + hi) / 2;
-                        const std::string m = col->ord_term(mid);
-                        if (upper ? !(key < m) : m < key) lo = mid + 1; else hi = mid;
-                    }
-                    return (int64_t)lo;
-                };
-                q.lo = 0;
-                q.hi = (int64_t)n - 1;
-                if (f.has_lower) {
-                    require(f.lo_term || f.lo_term_len == 0, ESGPU_ERR_INVALID, "keyword range without lower term bytes");
-                    q.lo = bound(f.lo_term, f.lo_term_len, !f.include_lower);
-                }
-                if (f.has_upper) {
-                    require(f.hi_term || f.hi_term_len == 0, ESGPU_ERR_INVALID, "keyword range without upper term bytes");
-                    q.hi = bound(f.hi_term, f.hi_term_len, f.include_upper) - 1;
-                }
+                const KeyInterval iv = ord_range_interval(col, f);
+                q.lo = iv.lo;
+                q.hi = iv.hi;
             }
             *bytes_per_doc += 4;
         } else if (col->type == ESGPU_COL_F64) {
             q.kind = PRED_F64_RANGE;
-            if (f.type == ESGPU_FILTER_TERM) { q.dlo = q.dhi = (double)f.term; q.lo_incl = q.hi_incl = 1; }
-            else {
-                q.dlo = f.has_lower ? f.lo_d : -INFINITY;
-                q.dhi = f.has_upper ? f.hi_d : INFINITY;
-                q.lo_incl = f.has_lower ? f.include_lower : 1;
-                q.hi_incl = f.has_upper ? f.include_upper : 1;
-            }
+            const F64Bounds fb = fm_f64_bounds(f);
+            q.dlo = fb.lo;
+            q.dhi = fb.hi;
+            q.lo_incl = fb.lo_incl;
+            q.hi_incl = fb.hi_incl;
             *bytes_per_doc += 8;
         } else {
             q.kind = PRED_I64_RANGE;
-            if (f.type == ESGPU_FILTER_TERM) { q.lo = q.hi = f.term; }
-            else {
-                int64_t lo = INT64_MIN, hi = INT64_MAX;
-                bool empty = false;
-                if (f.has_lower) {
-                    if (f.include_lower) lo = f.lo_i;
-                    else if (f.lo_i == INT64_MAX) empty = true;
-                    else lo = f.lo_i + 1;
-                }
-                if (f.has_upper) {
-                    if (f.include_upper) hi = f.hi_i;
-                    else if (f.hi_i == INT64_MIN) empty = true;
-                    else hi = f.hi_i - 1;
-                }
-                if (empty) { lo = 1; hi = 0; }
-                q.lo = lo;
-                q.hi = hi;
-            }
+            const KeyInterval iv = fm_long_interval(f);
+            q.lo = iv.lo;
+            q.hi = iv.hi;
             // single-valued: the compact copy of the column (u16 / u32 deltas) when its values span < 2^16 / 2^32
             if (compact_cols(p->ctx) && d16_on() && !col->multi && col->vmin <= col->vmax &&
                 (uint64_t)col->vmax - (uint64_t)col->vmin < (1ull << 16)) {
@@ -3123,24 +3133,27 @@ static void build_range_table(const std::vector<RangeBucket>& rb, bool f64, std:
     *n_cuts = n;
 }
 
-// RangeAggregator's collect of one segment (collect path 11): one launch of range_kernel over the range field and the
-// pipeline's metric field into the pipeline's [1][R] grid.  The query clauses and the accept bits are folded into one
-// doc bitset first (launch_filter_bits); the kernel evaluates no clause.
-static bool collect_range(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, const uint64_t* d_accept) {
-    const SpecNode& rn = p->specs[pl.outer];
-    const DevColumn* rc = s->col(pl.range_field.c_str());
-    if (!rc) return false;  // a segment without the field contributes nothing (ValuesSource null)
-    require(rc->type == ESGPU_COL_I64 || rc->type == ESGPU_COL_F64, ESGPU_ERR_UNSUPPORTED,
-            "range over a keyword or murmur3 field runs on the CPU path");
+// ---- what the range collect (path 11) and the filters collect (path 12) share on the host ----------------------------
+// Both fill a pipeline's [1][R] grid -- one cell per bucket, a doc's buckets a u64 mask -- from their own source of the
+// mask and the pipeline's metric field; RangeParams and FiltersParams name the fields of that part alike.
+
+// the pipeline's metric column in this segment (null: counts only, or an unmapped field, which collects nothing)
+static const DevColumn* mask_metric_column(const Pipeline& pl, const esgpu_segment* s, const char* under) {
     const DevColumn* mc = pl.met > 0 ? s->col(pl.metric_field.c_str()) : nullptr;
     if (mc) {
         require(mc->type == ESGPU_COL_I64 || mc->type == ESGPU_COL_F64, ESGPU_ERR_UNSUPPORTED,
-                "a metric over a non-numeric field under a range runs on the CPU path");
-        require(!mc->multi, ESGPU_ERR_UNSUPPORTED, "a multi-valued metric field under a range runs on the CPU path");
+                std::string("a metric over a non-numeric field under ") + under + " runs on the CPU path");
+        require(!mc->multi, ESGPU_ERR_UNSUPPORTED, std::string("a multi-valued metric field under ") + under + " runs on the CPU path");
     }
-    const uint32_t n_blocks = s->n_pad / kBlockDocs;
-    if (n_blocks == 0) return false;
-    const uint32_t R = (uint32_t)rn.rbuckets.size();
+    return mc;
+}
+
+// The grid of R cells for this segment (allocated at a request's first segment; the value counts split from the doc
+// counts when the metric field turns sparse), the metric column, the doc range, the grid pointers and the compensated
+// sums into P; the metric column's bytes into *bytes.  Returns the kernel's MET.
+template <class PARAMS>
+static int mask_collect_begin(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, const DevColumn* mc, uint32_t R, uint32_t n_blocks,
+                              PARAMS& P, uint64_t* bytes) {
     // (an unmapped metric field collects nothing: the doc counts alone, and the value counts split from them)
     const bool sparse_metric = pl.met > 0 && (!mc || mc->present.p);
     const bool first_segment = !pl.allocated || pl.fresh;
@@ -3167,29 +3180,12 @@ static bool collect_range(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, c
         pl.vcnt_mode = 1;
     }
     zero_counts(p, pl);
-    const int kind = rc->type == ESGPU_COL_F64 ? 2 : 1;
-    RangeParams P{};
-    {
-        std::vector<uint64_t> table;
-        build_range_table(rn.rbuckets, kind == 2, table, &P.n_cuts);
-        if (pl.rtable_kind != kind) {
-            if (!pl.d_rtable.p) pl.d_rtable.alloc(p->ctx, table.size() * 8);
-            HIPX(hipMemcpyAsync(pl.d_rtable.p, table.data(), table.size() * 8, hipMemcpyHostToDevice, p->stream));
-            HIPX(hipStreamSynchronize(p->stream));  // (the host table goes out of scope)
-            pl.rtable_kind = kind;
-        }
-    }
-    P.table = pl.d_rtable.as<uint64_t>();
-    P.R = R;
-    P.rv = rc->multi ? rc->values.p : wide_i64(p->ctx, rc, s, p->stream);  // (released upload-width values are rebuilt)
-    P.rv_present = rc->multi ? nullptr : rc->present.as<uint64_t>();
-    P.rv_off = rc->multi ? rc->offsets.as<uint64_t>() : nullptr;
-    P.rv_f64 = kind == 2;
     const int met = mc ? pl.met : 0;
     if (mc) {
-        P.mv = wide_i64(p->ctx, mc, s, p->stream);
+        P.mv = wide_i64(p->ctx, mc, s, p->stream);  // (released upload-width values are rebuilt)
         P.mv_present = mc->present.as<uint64_t>();
         P.mv_f64 = mc->type == ESGPU_COL_F64;
+        *bytes += 8ull * s->max_doc;
     }
     P.vcnt_mode = met > 0 ? pl.vcnt_mode : 0;
     P.n_docs = s->max_doc;
@@ -3222,9 +3218,15 @@ static bool collect_range(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, c
         P.g_sum_lo = lo(pl.g_sum_lo);
         if (met >= 3 && P.g_sq) P.g_sq_lo = lo(pl.g_sq_lo);
     }
-    // algorithmic bytes: each column at the width read, CSR offsets, the clause columns, the doc bitset
-    uint64_t bytes = rc->multi ? 8ull * rc->n_values + 8ull * s->max_doc : 8ull * s->max_doc;
-    if (mc) bytes += 8ull * s->max_doc;
+    return met;
+}
+
+// The query clauses and the accept bits folded into one doc bitset (launch_filter_bits; the kernels evaluate no clause),
+// then the launch over `cus x occupancy` workgroups and the folds of the compensated sums, between the pipeline's two
+// events.  occupancy() is asked when the launch configuration `okey` changes; launch(grid) starts the kernel.
+template <class PARAMS, class OCC, class LAUNCH>
+static void mask_collect_launch(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, const uint64_t* d_accept, PARAMS& P, uint32_t R,
+                                uint64_t okey, OCC occupancy, LAUNCH launch, uint64_t bytes, int path) {
     PredDev pred[kMaxPreds];
     int32_t npred = 0;
     uint64_t pred_bpd = 0;
@@ -3240,27 +3242,140 @@ static bool collect_range(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, c
     }
     P.accept = accept;
     if (accept) bytes += ((uint64_t)s->max_doc + 7) / 8;
-    const uint64_t okey = ((uint64_t)met << 1) | (rc->multi ? 1u : 0u);
     if (pl.occ_key != okey) {
-        pl.occ = range_occupancy(met, rc->multi);
+        pl.occ = occupancy();
         pl.occ_key = okey;
     }
     const uint32_t slots = std::max(1u, (uint32_t)p->ctx->cus * (uint32_t)pl.occ);
-    P.blocks_per_wg = (n_blocks + slots - 1) / slots;
-    const uint32_t grid = (n_blocks + P.blocks_per_wg - 1) / P.blocks_per_wg;
-    launch_range(P, met, grid, p->stream);
+    P.blocks_per_wg = (P.n_blocks + slots - 1) / slots;
+    launch((P.n_blocks + P.blocks_per_wg - 1) / P.blocks_per_wg);
     HIPX(hipGetLastError());
     if (P.g_sum_lo) launch_dd_fold(P.g_sum, P.g_sum_lo, R, p->stream);
     if (P.g_sq_lo) launch_dd_fold(P.g_sq, P.g_sq_lo, R, p->stream);
     HIPX(hipGetLastError());
     HIPX(hipEventRecord(pl.e1, p->stream));
     p->last_bytes += bytes;
-    p->last_path = 11;
+    p->last_path = path;
+}
+
+// RangeAggregator's collect of one segment (collect path 11): one launch of range_kernel over the range field and the
+// pipeline's metric field into the pipeline's [1][R] grid.  The query clauses and the accept bits are folded into one
+// doc bitset first (launch_filter_bits); the kernel evaluates no clause.
+static bool collect_range(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, const uint64_t* d_accept) {
+    const SpecNode& rn = p->specs[pl.outer];
+    const DevColumn* rc = s->col(pl.range_field.c_str());
+    if (!rc) return false;  // a segment without the field contributes nothing (ValuesSource null)
+    require(rc->type == ESGPU_COL_I64 || rc->type == ESGPU_COL_F64, ESGPU_ERR_UNSUPPORTED,
+            "range over a keyword or murmur3 field runs on the CPU path");
+    const DevColumn* mc = mask_metric_column(pl, s, "a range");
+    const uint32_t n_blocks = s->n_pad / kBlockDocs;
+    if (n_blocks == 0) return false;
+    const uint32_t R = (uint32_t)rn.rbuckets.size();
+    RangeParams P{};
+    // algorithmic bytes: each column at the width read, CSR offsets, the clause columns, the doc bitset
+    uint64_t bytes = rc->multi ? 8ull * rc->n_values + 8ull * s->max_doc : 8ull * s->max_doc;
+    const int met = mask_collect_begin(p, pl, s, mc, R, n_blocks, P, &bytes);
+    const int kind = rc->type == ESGPU_COL_F64 ? 2 : 1;
+    {
+        std::vector<uint64_t> table;
+        build_range_table(rn.rbuckets, kind == 2, table, &P.n_cuts);
+        if (pl.rtable_kind != kind) {
+            if (!pl.d_rtable.p) pl.d_rtable.alloc(p->ctx, table.size() * 8);
+            HIPX(hipMemcpyAsync(pl.d_rtable.p, table.data(), table.size() * 8, hipMemcpyHostToDevice, p->stream));
+            HIPX(hipStreamSynchronize(p->stream));  // (the host table goes out of scope)
+            pl.rtable_kind = kind;
+        }
+    }
+    P.table = pl.d_rtable.as<uint64_t>();
+    P.R = R;
+    P.rv = rc->multi ? rc->values.p : wide_i64(p->ctx, rc, s, p->stream);  // (released upload-width values are rebuilt)
+    P.rv_present = rc->multi ? nullptr : rc->present.as<uint64_t>();
+    P.rv_off = rc->multi ? rc->offsets.as<uint64_t>() : nullptr;
+    P.rv_f64 = kind == 2;
+    mask_collect_launch(
+        p, pl, s, d_accept, P, R, ((uint64_t)met << 1) | (rc->multi ? 1u : 0u), [&] { return range_occupancy(met, rc->multi); },
+        [&](uint32_t grid) { launch_range(P, met, grid, p->stream); }, bytes, 11);
+    return true;
+}
+
+static_assert(kFilterMaskCuts == kRangeCuts && kFilterMaskStride == kFilterStride, "the host tables are the kernel's");
+
+// FiltersAggregator's collect of one segment (collect path 12): one launch of filters_kernel over the distinct clause
+// columns of the aggregation's filters and the pipeline's metric field into the pipeline's [1][R] grid.  Every clause
+// becomes a key interval on its column (es_filter_masks.hpp: the normalisation set_preds uses), every clause column a
+// table of cuts and masks.  The query clauses and the accept bits are folded into one doc bitset first, as for the
+// range collect.
+static bool collect_filters(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, const uint64_t* d_accept) {
+    const SpecNode& fn = p->specs[pl.outer];
+    const uint32_t R = (uint32_t)fn.fkeys.size();
+    // the clause columns in order of first use, each with the clauses on it
+    struct ClauseCol {
+        const DevColumn* col;
+        std::vector<FilterClause> clauses;
+    };
+    std::vector<ClauseCol> ccols;
+    for (size_t k = 0; k < p->filters.size(); ++k) {
+        if (p->filter_owner[k] != pl.outer) continue;
+        const esgpu_filter& f = p->filters[k];
+        const DevColumn* col = s->col(p->filter_fields[k].c_str());
+        require(col != nullptr, ESGPU_ERR_UNSUPPORTED, "filter on a field missing from the segment");
+        require(!col->multi, ESGPU_ERR_UNSUPPORTED, "a filters aggregation over a multi-valued clause field runs on the CPU path");
+        require(col->type == ESGPU_COL_ORD_U32 || col->type == ESGPU_COL_I64 || col->type == ESGPU_COL_F64, ESGPU_ERR_UNSUPPORTED,
+                "a filters aggregation over a murmur3 clause field runs on the CPU path");
+        KeyInterval iv;
+        if (col->type == ESGPU_COL_ORD_U32) iv = f.type == ESGPU_FILTER_TERM ? KeyInterval{f.term, f.term} : ord_range_interval(col, f);
+        else if (col->type == ESGPU_COL_F64) iv = fm_f64_interval(fm_f64_bounds(f));
+        else iv = fm_long_interval(f);
+        size_t c = 0;
+        while (c < ccols.size() && ccols[c].col != col) ++c;
+        if (c == ccols.size()) {
+            require(ccols.size() < kFilterCols, ESGPU_ERR_UNSUPPORTED,
+                    "a filters aggregation over more than 4 clause fields runs on the CPU path");
+            ccols.push_back({col, {}});
+        }
+        ccols[c].clauses.push_back({f.slot, iv});
+    }
+    const DevColumn* mc = mask_metric_column(pl, s, "a filters aggregation");
+    FiltersParams P{};
+    std::vector<uint64_t> table(std::max<size_t>(ccols.size(), 1) * kFilterStride, 0);
+    uint64_t bytes = 0;
+    for (size_t c = 0; c < ccols.size(); ++c) {
+        const DevColumn* col = ccols[c].col;
+        const bool ord = col->type == ESGPU_COL_ORD_U32, f64 = col->type == ESGPU_COL_F64;
+        const KeyInterval domain = ord ? kOrdDomain : f64 ? fm_f64_domain() : KeyInterval{INT64_MIN, INT64_MAX};
+        require(build_filter_masks(ccols[c].clauses, fn.n_filters, domain, table.data() + c * kFilterStride, &P.col[c].n_cuts),
+                ESGPU_ERR_UNSUPPORTED, "a filters aggregation with more than 128 distinct clause bounds on one field runs on the CPU path");
+        P.col[c].kind = ord ? FCOL_ORD : f64 ? FCOL_F64 : FCOL_I64;
+        bytes += (ord ? 4ull : 8ull) * s->max_doc;
+    }
+    const uint32_t n_blocks = s->n_pad / kBlockDocs;
+    if (n_blocks == 0) return false;
+    const int met = mask_collect_begin(p, pl, s, mc, R, n_blocks, P, &bytes);
+    if (table != pl.ftable) {  // (the same request over the same dictionaries: the tables are on the device already)
+        if (pl.d_ftable.bytes < (size_t)kFilterCols * kFilterStride * 8) pl.d_ftable.alloc(p->ctx, (size_t)kFilterCols * kFilterStride * 8);
+        pl.ftable = std::move(table);  // the copy's source lives with the pipeline: the collect stays asynchronous
+        HIPX(hipMemcpyAsync(pl.d_ftable.p, pl.ftable.data(), pl.ftable.size() * 8, hipMemcpyHostToDevice, p->stream));
+    }
+    P.table = pl.d_ftable.as<uint64_t>();
+    P.n_cols = (uint32_t)ccols.size();
+    for (size_t c = 0; c < ccols.size(); ++c) {
+        const DevColumn* col = ccols[c].col;
+        // (released upload-width values are rebuilt)
+        P.col[c].v = col->type == ESGPU_COL_ORD_U32 ? col->ords().p : wide_i64(p->ctx, col, s, p->stream);
+        P.col[c].present = col->present.as<uint64_t>();
+    }
+    P.R = R;
+    P.other_bit = fn.other_bucket ? fn.n_filters : -1;
+    P.all_mask = fn.n_filters >= 64 ? ~0ull : (1ull << fn.n_filters) - 1ull;
+    mask_collect_launch(
+        p, pl, s, d_accept, P, R, 0x100u | (uint64_t)met, [&] { return filters_occupancy(met); },
+        [&](uint32_t grid) { launch_filters(P, met, grid, p->stream); }, bytes, 12);
     return true;
 }
 
 static bool collect_grid(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, const uint64_t* d_accept) {
     if (pl.range) return collect_range(p, pl, s, d_accept);
+    if (pl.filters) return collect_filters(p, pl, s, d_accept);
     const int done = collect_grid_cells(p, pl, s, d_accept);
     if (done == 1 && !pl.cards.empty()) collect_cards(p, pl, s, d_accept);
     return done != 0;
@@ -6570,11 +6685,43 @@ static Block build_range_root(esgpu_plan* p, const Group& g) {
     return r;
 }
 
+// FiltersAggregator.buildAggregation (:113-129) / buildEmptyAggregation (:132-146): every filter a bucket, in request
+// order, then the other bucket, with its doc count (pipes[0]'s cells) and its leaves from their pipelines' cells -- cell
+// == bucket position
+static Block build_filters_root(esgpu_plan* p, const Group& g) {
+    const SpecNode& n = p->specs[g.root];
+    Block r;
+    r.type = ESGPU_AGG_FILTERS;
+    r.name = n.name;
+    r.keyed = n.s.keyed;
+    r.boff.assign(1, 0);
+    r.term_off.assign(1, 0);
+    for (const Block& b : child_protos(p, g)) r.subs.push_back(b.like());
+    for (int pi : g.pipes) {
+        Pipeline& pl = p->pipes[pi];
+        if (pl.allocated) fetch_grid(p, pl);
+    }
+    bsync(p);
+    const Pipeline& P0 = p->pipes[g.pipes[0]];
+    begin_instance(r, 0);
+    for (size_t k = 0; k < n.fkeys.size(); ++k) {
+        push_bucket(r, (int64_t)k, &n.fkeys[k], P0.allocated ? (int64_t)P0.hc.cnt[k] : 0);
+        for (size_t ki = 0; ki < g.kids.size(); ++ki) {
+            const Pipeline& L = p->pipes[g.kids[ki].leaf.pipe];
+            if (L.allocated) append_leaf(p, L, g.kids[ki].leaf.leaf, k, r.subs[ki]);
+            else r.subs[ki].append_empty();
+        }
+    }
+    end_instance(r);
+    return r;
+}
+
 static Block build_group(esgpu_plan* p, const Group& g) {
     Pipeline& P0 = p->pipes[g.pipes[0]];
     if (P0.kind == 1) return build_cardinality(p, P0);
     const int t = p->specs[g.root].s.type;
     if (t == ESGPU_AGG_RANGE) return build_range_root(p, g);
+    if (t == ESGPU_AGG_FILTERS) return build_filters_root(p, g);
     if (is_metric(t)) return build_metric_root(p, g);
     if (t == ESGPU_AGG_TERMS) return build_terms_root(p, g);
     return build_hist_root(p, g);

@@ -253,7 +253,22 @@ enum {
      * ESGPU_FORMAT_NUMBER on the range (its keys would need DecimalFormat); a date format other than the mapping's
      * default (strict_date_optional_time, with or without ||epoch_millis), which is all the date printer prints.
      * date_range, ip_range, geo_distance and string bounds (date math) are not covered. */
-    ESGPU_AGG_RANGE = 13
+    ESGPU_AGG_RANGE = 13,
+    /* FiltersAggregator (A/bucket/filters/FiltersAggregator.java): one bucket per filter of esgpu_agg_spec.filter_keys, in
+     * request order, and after them the other bucket (other_bucket) of the docs matching none.  Filter i is the conjunction
+     * of the esgpu_filter clauses with owner = this spec + 1 and slot = i; a filter without a clause is match_all.  A doc
+     * is in every bucket whose filter it matches.  Clauses: ESGPU_FILTER_TERM / ESGPU_FILTER_RANGE over single-valued
+     * keyword, long / date and double columns, dense or sparse (a doc without a value matches no clause on the column).
+     * Sub-aggregations: stats, extended_stats, avg, sum, min, max, value_count over single-valued long / double fields.
+     * Result block: n_buckets = the buckets per instance, doc_counts, subs, the keys in term_offsets / term_bytes, keyed.
+     * A plan built without a collect has every bucket, the other one included, with count 0.
+     * Refused with ESGPU_ERR_INVALID: no filter.  Refused with ESGPU_ERR_UNSUPPORTED at esgpu_plan_create (the plugin
+     * keeps the Java aggregator): more than 64 buckets, the other bucket included (a doc's buckets are one u64 mask); a
+     * filters aggregation that is not top level; a bucket, filter or cardinality sub-aggregation.  Refused with
+     * ESGPU_ERR_UNSUPPORTED at the first collect that shows it: more than 4 distinct clause columns; more than 128
+     * distinct cuts (clause bounds) on one column; a multi-valued or ESGPU_COL_U64 clause column; a clause field missing
+     * from the segment; a non-numeric or multi-valued metric field. */
+    ESGPU_AGG_FILTERS = 14
 };
 
 /* One range of an ESGPU_AGG_RANGE spec (RangeAggregator.Range): [from, to) on doubles; -Infinity / +Infinity = an
@@ -351,6 +366,12 @@ typedef struct esgpu_agg_spec {
     const esgpu_range* ranges;
     int32_t n_ranges;
     int32_t reserved_ranges;
+    /* filters (FiltersParser.java:60-113): the filters' keys in request order -- `keyed` 1: the named form; 0: the
+     * anonymous form, whose keys are "0", "1", ... -- and the other bucket (other_bucket_key NULL = "_other_") */
+    const char* const* filter_keys;
+    int32_t n_filters;
+    int32_t other_bucket;
+    const char* other_bucket_key;
 } esgpu_agg_spec;
 
 enum {
@@ -373,14 +394,19 @@ typedef struct esgpu_filter {
     int32_t has_lower;
     int32_t has_upper;
     int32_t owner;                /* 0 = query clause (applies to every aggregation); k + 1 = clause of the filter
-                                     aggregation spec[k] (FilterAggregator: conjunction of its clauses) */
+                                     aggregation spec[k] (FilterAggregator: conjunction of its clauses) or of filter
+                                     `slot` of the filters aggregation spec[k] */
     const char* field;
     int64_t term;                 /* TERM on I64 / ORD columns */
-    int64_t lo_i, hi_i;           /* RANGE on I64 / U64 columns */
+    int64_t lo_i, hi_i;           /* RANGE on I64 / U64 columns (a bound whose lo_d / hi_d is +-Infinity is that infinity
+                                     on an I64 column too: lo_i / hi_i are then not read) */
     double lo_d, hi_d;            /* RANGE on F64 columns */
     const uint8_t* lo_term;       /* RANGE on ORD columns: bounds as term bytes, compared as unsigned bytes (BytesRef) */
     const uint8_t* hi_term;
     uint64_t lo_term_len, hi_term_len;
+    int32_t slot;                 /* a clause whose owner is an ESGPU_AGG_FILTERS spec: the filter of that spec it belongs
+                                     to (index into filter_keys); 0 otherwise */
+    int32_t reserved_slot;
 } esgpu_filter;
 
 int esgpu_terms_thresholds(int32_t size, int32_t shard_size, int64_t min_doc_count, int64_t shard_min_doc_count,
@@ -449,7 +475,10 @@ int esgpu_plan_destroy(esgpu_plan* plan);
  * filtered request (the scatter form deferred to the top-k), 10 LDS key window over the top-ranked terms (the segment
  * is retained -- esgpu_plan_deferred_segments -- and collected again over every term if the request brings a second),
  * 11 the range collect (one pass over the range field and one metric field per pipeline; bytes: each column at the 8
- * bytes read, CSR offsets, the doc bitset of a filtered request and the columns its clauses read). */
+ * bytes read, CSR offsets, the doc bitset of a filtered request and the columns its clauses read), 12 the filters collect
+ * (one pass over the distinct clause columns and one metric field per pipeline; bytes: each distinct clause column once
+ * at the width read -- 4 for ordinals, 8 otherwise --, the metric column at 8, the doc bitset of a filtered request and
+ * the columns that bitset's clauses read). */
 int esgpu_plan_last_collect_stats(const esgpu_plan* plan, double* kernel_ms, uint64_t* algorithmic_bytes,
                                   int32_t* path);
 /* The kernel that ran the last collect's LDS-window launch: 0 the generic collect kernel, 1 the ranked kernel (path 10
@@ -574,11 +603,11 @@ int esgpu_result_to_json(const esgpu_result* r, char* buf, size_t cap, size_t* n
 int esgpu_result_to_xcontent(const esgpu_result* r, char* buf, size_t cap, size_t* needed);
 /* Elasticsearch's transport wire format of a shard result: the bytes InternalAggregations.writeTo(StreamOutput) writes
  * (InternalAggregations.java:215-222) -- per aggregation its AggregationStreams type ("sterms", "dhisto", "histo",
- * "stats", "estats", "avg", "cardinality", "filter", "range"), InternalAggregation.writeTo (name, null metadata, no pipeline
+ * "stats", "estats", "avg", "cardinality", "filter", "range", "filters"), InternalAggregation.writeTo (name, null metadata, no pipeline
  * aggregators, InternalAggregation.java:212-221) and the class's doWriteTo (StringTerms.java:205-217 + Bucket.writeTo
  * :128-136, InternalHistogram.java:510-523 + Bucket.writeTo :183-187 + EmptyBucketInfo :223-230, InternalStats.java:
  * 182-189, InternalExtendedStats.java:169-174, InternalAvg.java:102-106, InternalCardinality.java:92-100 +
- * HyperLogLogPlusPlus.writeTo :519-535, InternalSingleBucketAggregation.java:124-127, InternalRange.java:323-337), with
+ * HyperLogLogPlusPlus.writeTo :519-535, InternalSingleBucketAggregation.java:124-127, InternalRange.java:323-337, InternalFilters.java:245-251), with
  * StreamOutput's encodings
  * (vInt/vLong, big-endian long/int, writeString as Java chars in modified UTF-8, StreamOutput.java:118-270).
  * A JNI shim hands these bytes to StreamInput and InternalAggregations.readAggregations to get the Java objects.

@@ -29,19 +29,23 @@ def variants():
     ns = lambda m: AB.terms("hosts").field("host").size(10).subAggregation(  # noqa: E731
         AB.dateHistogram("h").field("@timestamp").interval("1h").subAggregation(m))
     # five latency classes over response_time_ms, each with stats(bytes): as one range aggregation (one pass over the two
-    # columns) and as its twin, five top-level filter aggregations with a gte / lt range clause and the same child
+    # columns), as its twin, five top-level filter aggregations with a gte / lt range clause and the same child, and as
+    # one filters aggregation of the same five clauses (one pass over the two columns)
     cuts = [None, 50, 100, 250, 500, None]
     rng = AB.range("lat").field("response_time_ms").subAggregation(AB.stats("b").field("bytes"))
     flt5 = []
+    fagg = AB.filters("lat").subAggregation(AB.stats("b").field("bytes"))
     for k, (lo, hi) in enumerate(zip(cuts[:-1], cuts[1:])):
         rng.addRange(float("-inf") if lo is None else lo, float("inf") if hi is None else hi)
         q = QB.rangeQuery("response_time_ms")
         q = q if lo is None else q.gte(lo)
         q = q if hi is None else q.lt(hi)
         flt5.append(AB.filter("f%d" % k, q).subAggregation(AB.stats("b").field("bytes")))
+        fagg.filter("f%d" % k, q)
     return {
         "range5_stats": ([rng], None),
         "filters5_stats": (flt5, None),
+        "filters_agg5_stats": ([fagg], None),
         "terms_host": ([AB.terms("hosts").field("host")], None),
         "date_hist": ([AB.dateHistogram("h").field("@timestamp").interval("1h")], None),
         "config2_dh_ext": ([AB.dateHistogram("h").field("@timestamp").interval("1h").subAggregation(
