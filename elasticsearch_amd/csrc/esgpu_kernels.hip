@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "es_common.hpp"
+#include "es_pack12.hpp"
 #include "esgpu_kernels.hpp"
 
 namespace esgpu {
@@ -1725,6 +1726,24 @@ __global__ void rank8_kernel(const uint16_t* src, uint32_t n8, uint8_t* out) {
 void launch_rank8(const uint16_t* rank16, uint32_t n, uint8_t* out, hipStream_t st) {
     const uint32_t n8 = n / 8;
     if (n8) hipLaunchKernelGGL(rank8_kernel, dim3(std::min<uint32_t>(8192, (n8 + 255) / 256)), dim3(256), 0, st, rank16, n8, out);
+}
+// d12 (DevColumn): 16-bit metric deltas, all below 4096, in the packed 12-bit form of es_pack12.hpp -- a group of 8 docs
+// per thread, one 16-byte load and three word stores; n is a multiple of 8 (n_pad)
+__global__ void d12_kernel(const uint16_t* src, uint32_t n8, uint32_t* out) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += gridDim.x * blockDim.x) {
+        const u32x4_t v = load16(src + (size_t)i * kP12Group);
+        const uint32_t d[8] = {v.x & 0xFFFFu, v.x >> 16, v.y & 0xFFFFu, v.y >> 16, v.z & 0xFFFFu, v.z >> 16, v.w & 0xFFFFu, v.w >> 16};
+        uint32_t w[3];
+        p12_pack8(d, w);
+        uint32_t* const o = out + (size_t)i * kP12Words;
+        o[0] = w[0];
+        o[1] = w[1];
+        o[2] = w[2];
+    }
+}
+void launch_d12(const uint16_t* d16, uint32_t n, void* out, hipStream_t st) {
+    const uint32_t n8 = n / kP12Group;
+    if (n8) hipLaunchKernelGGL(d12_kernel, dim3(std::min<uint32_t>(8192, (n8 + 255) / 256)), dim3(256), 0, st, d16, n8, (uint32_t*)out);
 }
 __global__ void delta32_kernel(const int64_t* v, uint32_t n, int64_t base, uint32_t* out) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)

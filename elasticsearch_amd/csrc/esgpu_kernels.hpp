@@ -158,13 +158,14 @@ struct CollectParams {
     uint32_t n_chunks;
 };
 
-// The ranked kernel (esgpu_ranked.hip) reads only this of a path-10 collect: the rank and 16-bit metric-delta columns, the
+// The ranked kernel (esgpu_ranked.hip) reads only this of a path-10 collect: the rank and metric-delta columns, the
 // block-delta key column, the zone keys, the packed-cell geometry and the grid.  Fields are CollectParams' of the same
 // name unless noted.
 struct RankedParams {
     const void* rank;  // each doc's frequency rank: TermRanks' rank8 (one byte, 0xFF = rank >= 255 or missing) or rank16
                        // (CollectParams.ord16 of a ranked collect), as the launch's rank width says
-    const uint16_t* mv16;
+    const void* mv;    // the metric's deltas over mv_base: the column's d16 (CollectParams.mv16) or its packed 12-bit d12
+                       // (es_pack12.hpp), as the launch's metric width says
     const uint16_t* hv16;
     const int64_t* hv16_base;
     const uint8_t* hv8;
@@ -463,9 +464,10 @@ size_t collect_lds_bytes(uint32_t T, uint32_t W, int met, int vcnt_mode, int ocn
 int collect_occupancy(bool ord, int hk, int met, size_t lds, int vk, bool wide = false);
 // the ranked-terms collect over time-sorted block-delta keys (esgpu_ranked.hip): met 1 avg, 2 stats; grid = static
 // ranges of blocks_per_wg blocks; lds = collect_lds_bytes of the same packed cells
-// rw: bytes per rank (1: RankedParams.rank is rank8, 2: rank16)
-void launch_ranked(const RankedParams& p, int met, int rw, uint32_t grid, size_t lds, hipStream_t s);
-int ranked_occupancy(int met, int rw, size_t lds);
+// rw: bytes per rank (1: RankedParams.rank is rank8, 2: rank16); mw: bits per metric delta (16: RankedParams.mv is d16,
+// 12: d12 -- with rw 1 only)
+void launch_ranked(const RankedParams& p, int met, int rw, int mw, uint32_t grid, size_t lds, hipStream_t s);
+int ranked_occupancy(int met, int rw, int mw, size_t lds);
 // returns whether the group floors and snapshot are left as lower bounds of the registers (HllParams.snap_ok for the
 // request's next segment)
 bool launch_hll(const HllParams& p, uint32_t cus, hipStream_t s);
@@ -527,6 +529,8 @@ void launch_pack_ord16(const uint32_t* src, uint32_t n, uint16_t* out, hipStream
 void launch_rank_ord16(const uint16_t* ord16, uint32_t n, const uint16_t* rank_of, uint32_t T, uint16_t* out, hipStream_t st);
 // ranked terms: the 16-bit ranks saturated to a byte, min(rank, 255) (0xFFFF -> 0xFF); n a multiple of 16
 void launch_rank8(const uint16_t* rank16, uint32_t n, uint8_t* out, hipStream_t st);
+// d12: n (a multiple of 8) 16-bit deltas below 4096 into the packed 12-bit form of es_pack12.hpp (3 n / 2 bytes)
+void launch_d12(const uint16_t* d16, uint32_t n, void* out, hipStream_t st);
 // ---- numeric ordinals (esgpu_numord.hip): a long column's sorted distinct values and each doc's rank among them ----
 // `v` with `width` 8 is the upload-width column, 4 / 2 its d32 / d16 deltas over vmin; span = vmax - vmin; the bitmap
 // holds span / 64 + 1 zeroed 64-bit words.  Spans below kNumOrdLdsBits are marked in a per-workgroup LDS bitmap.

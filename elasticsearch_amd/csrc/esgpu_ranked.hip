@@ -1,5 +1,6 @@
 // esgpu_ranked.hip — the ranked-terms collect (path 10) over the rank column (8-bit rank8, or the 16-bit rank16 it is
-// recoded from), the 16-bit metric deltas and block-delta keys of time-sorted data: a kernel of its own for the one shape
+// recoded from), the metric deltas (16-bit d16, or the packed 12-bit d12 recoded from it when the values span < 4096)
+// and block-delta keys of time-sorted data: a kernel of its own for the one shape
 // that path runs at, in place of the generic collect_kernel
 // (esgpu_collect.hpp), whose step loop carries multi-pass groups, the global-grid fallback, per-step prefetch scheduling
 // and the whole CollectParams block for shapes this path never sees.
@@ -14,6 +15,7 @@
 //     global atomics.  Correct for any data; it is not the fast path.
 // The LDS cells are collect_kernel's packed cells ([W keys][K ranks] count << pk_shift | sum of deltas in lane-rotated
 // copies cstride apart, and one (min, max) delta pair per cell), and the flush decodes them as flush_window_pi does.
+#include "es_pack12.hpp"
 #include "esgpu_collect.hpp"
 
 namespace esgpu {
@@ -88,6 +90,42 @@ template <> struct rk_r8<2> {
     __device__ __forceinline__ rk_r4<2> hi() const { return {v.z, v.w}; }
 };
 
+// The metric deltas at their two widths (MW bits per doc).  rk_m8: a thread's 8 docs of one buffer -- MW 16 one 16-byte
+// load of d16, MW 12 the three words of d12's group (es_pack12.hpp: one 12-byte load, 4-byte aligned).  quad(h, d): the
+// deltas of docs 4 h .. 4 h + 3; pair(i): a word holding docs 2 i and 2 i + 1 -- doc j's delta is
+// (pair >> (even + (j & 1) * step)) & mask, which is how the per-doc body takes it.
+typedef unsigned int u32x3_t __attribute__((ext_vector_type(3)));
+typedef u32x3_t u32x3_a4_t __attribute__((aligned(4)));
+template <int MW> struct rk_m8;
+template <> struct rk_m8<16> {
+    u32x4_t v;
+    __device__ __forceinline__ void load(const void* col, size_t doc) { v = rk_load16((const uint16_t*)col + doc); }
+    static constexpr uint32_t even = 0, step = 16, mask = 0xFFFFu;
+    __device__ __forceinline__ uint32_t pair(int i) const { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
+    __device__ __forceinline__ void quad(int h, uint32_t (&d)[4]) const {
+        const uint32_t m0 = pair(2 * h), m1 = pair(2 * h + 1);
+        d[0] = m0 & 0xFFFFu; d[1] = m0 >> 16; d[2] = m1 & 0xFFFFu; d[3] = m1 >> 16;
+    }
+};
+template <> struct rk_m8<12> {
+    u32x3_t v;
+    static constexpr uint32_t even = kP12Even, step = kP12Odd - kP12Even, mask = kP12Mask;
+    __device__ __forceinline__ void load(const void* col, size_t doc) {  // doc: a multiple of kP12Group, 1.5 bytes each
+        const u32x3_a4_t* const p = reinterpret_cast<const u32x3_a4_t*>((const uint8_t*)col + doc + (doc >> 1));
+#if ESGPU_RK_NT
+        v = __builtin_nontemporal_load(p);
+#else
+        v = *p;
+#endif
+    }
+    __device__ __forceinline__ uint32_t pair(int i) const { return p12_window(v.x, v.y, v.z, i); }
+    __device__ __forceinline__ void quad(int h, uint32_t (&d)[4]) const {
+        const uint32_t x0 = p12_window(v.x, v.y, v.z, 2 * h), x1 = p12_window(v.x, v.y, v.z, 2 * h + 1);
+        d[0] = p12_even(x0); d[1] = p12_odd(x0); d[2] = p12_even(x1); d[3] = p12_odd(x1);
+    }
+};
+static_assert(kRkDocs == kP12Group, "a thread's 8 docs of a buffer are one group of d12");
+
 // 4 docs of a single-key block: their ranks (rk_r4) and metric deltas.  `rowm` is the LDS address of
 // the block's row of (min, max) pairs, `dpk` the lane's distance from a pair to the packed word of the same cell in the
 // lane's copy, `missm` the pair of the spare cell (index K * W: never flushed, its pair (0, ~0) never moves), where the
@@ -95,11 +133,10 @@ template <> struct rk_r8<2> {
 // adds, one wait for the reads; the bound atomics only where a bound moves.  MET 1 (avg): no pairs -- `rowm` / `missm`
 // then address the packed words of the lane's copy themselves and dpk is 0.
 template <int MET, int RW>
-__device__ __forceinline__ void rk_quad(rk_r4<RW> r, uint32_t m0, uint32_t m1, uint32_t K, uint32_t rowm,
+__device__ __forceinline__ void rk_quad(rk_r4<RW> r, const uint32_t (&dv)[4], uint32_t K, uint32_t rowm,
                                         uint32_t missm, uint32_t dpk, uint32_t onehi) {
     uint32_t t[4];
     r.unpack(t);
-    const uint32_t dv[4] = {m0 & 0xFFFFu, m0 >> 16, m1 & 0xFFFFu, m1 >> 16};
     uint32_t ca[4], mlo[4], mhi[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {  // (a rank past K, the missing rank 0xFFFF / 0xFF included, is not collected)
@@ -124,8 +161,10 @@ __device__ __forceinline__ void rk_quad(rk_r4<RW> r, uint32_t m0, uint32_t m1, u
     }
 }
 
-template <int MET, int RW>
+// MW: bits per metric delta (RankedParams.mv: 16 d16, 12 d12 -- the 12-bit form exists with the 8-bit ranks only)
+template <int MET, int RW, int MW>
 __global__ __launch_bounds__(kRkWG, ESGPU_RK_WAVES) void ranked_kernel(RankedParams P) {
+    static_assert(MW == 16 || (MW == 12 && RW == 1), "d12 is streamed beside rank8");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t K = P.K, W = P.W, C = K * W;
     const uint32_t ncp = max(P.ncopies, 1u);
@@ -207,9 +246,10 @@ __global__ __launch_bounds__(kRkWG, ESGPU_RK_WAVES) void ranked_kernel(RankedPar
     };
 
     // any block, doc by doc: 4 docs of the thread (docs doc0 .. doc0 + 3, their ranks and metric words as the block's
-    // buffers hold them -- the columns are not read again) with their keys by the block-delta unpack, slots by the magic
-    // division of the value's distance from the block's first key (the zone map bounds the block's values, so the
-    // distance is non-negative and below the block's keys x interval; a block spanning 2^32 or more divides in 64 bits)
+    // buffers hold them, the metric as rk_m8's pair words -- the columns are not read again) with their keys by the
+    // block-delta unpack, slots by the magic division of the value's distance from the block's first key (the zone map
+    // bounds the block's values, so the distance is non-negative and below the block's keys x interval; a block spanning
+    // 2^32 or more divides in 64 bits)
     auto slow_quad = [&](uint32_t doc0, rk_r4<RW> r, uint32_t m0, uint32_t m1, int64_t kmn, int64_t kmx) {
         const auto& Q = *rk_again();
         const int64_t vb = (Q.key0 + kmn) * Q.interval + Q.offset;  // the first instant of key kmn
@@ -225,7 +265,7 @@ __global__ __launch_bounds__(kRkWG, ESGPU_RK_WAVES) void ranked_kernel(RankedPar
             for (uint32_t j = 0; j < nd; ++j) {
                 const uint32_t m2 = j < 2 ? m0 : m1, t2 = j < 2 ? tw.x : tw.y;
                 const uint32_t hs = (j & 1u) * 16u;
-                const uint32_t t = r.at(j), dv = (m2 >> hs) & 0xFFFFu;
+                const uint32_t t = r.at(j), dv = (m2 >> (rk_m8<MW>::even + (j & 1u) * rk_m8<MW>::step)) & rk_m8<MW>::mask;
                 if (t >= K) continue;
                 const int64_t v = b + (int64_t)(((t2 >> hs) & 0xFFFFu) | (((hb >> (8u * j)) & 0xFFu) << 16));
                 const int64_t k = d32 ? kmn + (int64_t)magic_div((uint32_t)((uint64_t)v - (uint64_t)vb), Q.mg_m, Q.mg_s1,
@@ -267,10 +307,11 @@ __global__ __launch_bounds__(kRkWG, ESGPU_RK_WAVES) void ranked_kernel(RankedPar
     const uint32_t tid8 = threadIdx.x * kRkDocs;
     i64x2_t z = zk[__builtin_amdgcn_readfirstlane(b_begin)];
     rk_r8<RW> ra, rb;
+    rk_m8<MW> ma, mb;
     ra.load(P.rank, (size_t)b_begin * kBlockDocs + tid8);
-    u32x4_t ma = rk_load16(P.mv16 + (size_t)b_begin * kBlockDocs + tid8);
+    ma.load(P.mv, (size_t)b_begin * kBlockDocs + tid8);
     rb.load(P.rank, (size_t)b_begin * kBlockDocs + kRkStepDocs + tid8);
-    u32x4_t mb = rk_load16(P.mv16 + (size_t)b_begin * kBlockDocs + kRkStepDocs + tid8);
+    mb.load(P.mv, (size_t)b_begin * kBlockDocs + kRkStepDocs + tid8);
 #pragma unroll 1
     for (uint32_t cb = b_begin; cb < b_end; ++cb) {
         const int64_t kmn = z.x, kmx = z.y;
@@ -291,49 +332,54 @@ __global__ __launch_bounds__(kRkWG, ESGPU_RK_WAVES) void ranked_kernel(RankedPar
         const bool fast = kmn == kmx && (uint64_t)kmn < (uint64_t)P.H && (uint64_t)(cb + 1) * kBlockDocs <= P.n_docs;
         if (!fast && any) {
             const uint32_t d0 = cb * kBlockDocs + tid8;
-            slow_quad(d0, ra.lo(), ma.x, ma.y, kmn, kmx);
-            slow_quad(d0 + 4u, ra.hi(), ma.z, ma.w, kmn, kmx);
-            slow_quad(d0 + kRkStepDocs, rb.lo(), mb.x, mb.y, kmn, kmx);
-            slow_quad(d0 + kRkStepDocs + 4u, rb.hi(), mb.z, mb.w, kmn, kmx);
+            slow_quad(d0, ra.lo(), ma.pair(0), ma.pair(1), kmn, kmx);
+            slow_quad(d0 + 4u, ra.hi(), ma.pair(2), ma.pair(3), kmn, kmx);
+            slow_quad(d0 + kRkStepDocs, rb.lo(), mb.pair(0), mb.pair(1), kmn, kmx);
+            slow_quad(d0 + kRkStepDocs + 4u, rb.hi(), mb.pair(2), mb.pair(3), kmn, kmx);
         }
         dirty = dirty || any;
         // each buffer has one reload per block, outside the branches: a reload under a branch gives the buffer two
         // definitions, which the compiler joins by copying the loaded registers -- a vmcnt(0) wait per block
         const uint32_t rowm = cell0 + 8u * (((uint32_t)kmn - win0) * K);
         if (fast) {
-            rk_quad<MET, RW>(ra.lo(), ma.x, ma.y, K, rowm, missm, dpk, onehi);
-            rk_quad<MET, RW>(ra.hi(), ma.z, ma.w, K, rowm, missm, dpk, onehi);
+            uint32_t dv[4];
+            ma.quad(0, dv);
+            rk_quad<MET, RW>(ra.lo(), dv, K, rowm, missm, dpk, onehi);
+            ma.quad(1, dv);
+            rk_quad<MET, RW>(ra.hi(), dv, K, rowm, missm, dpk, onehi);
         }
         ra.load(P.rank, nd0);
-        ma = rk_load16(P.mv16 + nd0);
+        ma.load(P.mv, nd0);
         if (fast) {
-            rk_quad<MET, RW>(rb.lo(), mb.x, mb.y, K, rowm, missm, dpk, onehi);
-            rk_quad<MET, RW>(rb.hi(), mb.z, mb.w, K, rowm, missm, dpk, onehi);
+            uint32_t dv[4];
+            mb.quad(0, dv);
+            rk_quad<MET, RW>(rb.lo(), dv, K, rowm, missm, dpk, onehi);
+            mb.quad(1, dv);
+            rk_quad<MET, RW>(rb.hi(), dv, K, rowm, missm, dpk, onehi);
         }
         rb.load(P.rank, nd1);
-        mb = rk_load16(P.mv16 + nd1);
+        mb.load(P.mv, nd1);
     }
     if (dirty) flush();
 }
 
-// rw: the rank column's width in bytes (RankedParams.rank: 1 rank8, 2 rank16)
-template <int MET, int RW>
-static void launch_rk(const RankedParams& p, uint32_t grid, size_t lds, hipStream_t st) {
-    hipLaunchKernelGGL((ranked_kernel<MET, RW>), dim3(grid), dim3(kRkWG), lds, st, p);
+// rw: the rank column's width in bytes (RankedParams.rank: 1 rank8, 2 rank16); mw: the metric deltas' width in bits
+// (RankedParams.mv: 16 d16, 12 d12, which goes with rw 1).  with_rk: the instantiation of a launch's (met, rw, mw).
+template <typename F>
+static auto with_rk(int met, int rw, int mw, F&& f) {
+    if (met >= 2) {
+        if (rw == 1) return mw == 12 ? f(ranked_kernel<2, 1, 12>) : f(ranked_kernel<2, 1, 16>);
+        return f(ranked_kernel<2, 2, 16>);
+    }
+    if (rw == 1) return mw == 12 ? f(ranked_kernel<1, 1, 12>) : f(ranked_kernel<1, 1, 16>);
+    return f(ranked_kernel<1, 2, 16>);
 }
-void launch_ranked(const RankedParams& p, int met, int rw, uint32_t grid, size_t lds, hipStream_t st) {
-    if (met >= 2) rw == 1 ? launch_rk<2, 1>(p, grid, lds, st) : launch_rk<2, 2>(p, grid, lds, st);
-    else rw == 1 ? launch_rk<1, 1>(p, grid, lds, st) : launch_rk<1, 2>(p, grid, lds, st);
+void launch_ranked(const RankedParams& p, int met, int rw, int mw, uint32_t grid, size_t lds, hipStream_t st) {
+    with_rk(met, rw, mw, [&](auto* k) { hipLaunchKernelGGL(k, dim3(grid), dim3(kRkWG), lds, st, p); return 0; });
 }
-
-template <int MET, int RW>
-static hipError_t occ_rk(int* n, size_t lds) {
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(n, ranked_kernel<MET, RW>, kRkWG, lds);
-}
-int ranked_occupancy(int met, int rw, size_t lds) {
+int ranked_occupancy(int met, int rw, int mw, size_t lds) {
     int n = 0;
-    const hipError_t e = met >= 2 ? (rw == 1 ? occ_rk<2, 1>(&n, lds) : occ_rk<2, 2>(&n, lds))
-                                  : (rw == 1 ? occ_rk<1, 1>(&n, lds) : occ_rk<1, 2>(&n, lds));
+    const hipError_t e = with_rk(met, rw, mw, [&](auto* k) { return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, kRkWG, lds); });
     return e == hipSuccess ? n : 1;
 }
 

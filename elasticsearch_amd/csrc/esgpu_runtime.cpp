@@ -36,6 +36,7 @@
 
 #include "../../include/esgpu.h"
 #include "es_common.hpp"
+#include "es_pack12.hpp"
 #include "es_rounding.hpp"
 #include "es_term_rank.hpp"
 #include "es_filter_masks.hpp"
@@ -90,8 +91,9 @@ extern "C" int esgpu_ctx_set_option(esgpu_ctx* c, int32_t option, int64_t value)
             c->opt_num_max = value;
             return;
         }
-        if (option == ESGPU_OPT_RANKED_TERMS) {  // (2: path 10 on the generic collect kernel, 3: the ranked kernel over rank16)
-            require(value >= 0 && value <= 3, ESGPU_ERR_INVALID, "ranked terms option must be 0..3");
+        // (2: path 10 on the generic collect kernel, 3: the ranked kernel over rank16, 4: over rank8 and d16)
+        if (option == ESGPU_OPT_RANKED_TERMS) {
+            require(value >= 0 && value <= 4, ESGPU_ERR_INVALID, "ranked terms option must be 0..4");
             c->opt_ranked = (int)value;
             return;
         }
@@ -354,6 +356,11 @@ struct DevColumn {
     // with the column): ords() in 16 bits (0xFFFF missing) while the dictionary has fewer than 65,535 terms -- keyed by
     // the ords() buffer it was made from -- and a long column's values as 32-bit deltas over vmin while vmax - vmin < 2^32
     DevBuf ord16, d32, d16;  // d16: the same deltas in 16 bits while vmax - vmin < 2^16 (ensure_d16)
+    // d16's deltas again at 12 bits each, packed (es_pack12.hpp: n_pad * 3 / 2 bytes), while vmax - vmin < 4096 -- what
+    // the ranked kernel streams in place of d16, built from d16 the first time a collect decides on that kernel for the
+    // column (ensure_d12: +1.5 B per doc of HBM, only for segments that reach it)
+    DevBuf d12;
+    bool d12_done = false;  // tried (d12 null: being built on another thread, or over the HBM budget)
     // block deltas of a dense key column (ensure_b16): per run of kB16Docs docs its minimum (b16_base) and a 16-bit delta
     // per doc, when every run spans < 2^16 -- time-sorted timestamps at any density above ~1 doc per 32 ms -- and, when
     // some run spans 2^16 or more but none 2^24 (roughly time-ordered data: ±1 h of displacement), bits 16..23 of every
@@ -1953,6 +1960,7 @@ static const TermRanks* ensure_term_ranks(esgpu_ctx* c, const DevColumn* col, co
                                           hipStream_t st);
 static bool ranked_terms_on(const esgpu_ctx* c);
 static const uint8_t* ensure_rank8(esgpu_ctx* c, const TermRanks* rk, const esgpu_segment* s, hipStream_t st);
+static const void* ensure_d12(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
 static const DevColumn* terms_col(esgpu_plan* p, const esgpu_segment* s, const std::string& field);
 static const DevColumn* value_count_metric(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s);
 static const uint32_t* ensure_d32(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
@@ -3942,19 +3950,23 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
     // choice uses), in packed cells with lane-rotated copies (each copy then has a spare cell past the window's, where
     // the kernel sends the docs it does not collect).  Its per-doc body divides by the interval in 32 bits.
     // ESGPU_OPT_RANKED_TERMS = 2 keeps path 10 on collect_kernel; 3 keeps the ranked kernel on the 16-bit ranks, which 1
-    // takes only when the segment's rank8 product does not fit the HBM budget.
+    // takes only when the segment's rank8 product does not fit the HBM budget; 4 keeps it on rank8 and d16, which 1 takes
+    // when the metric spans 4096 or more, or its d12 product does not fit.
     const int opt_rk = p->ctx->opt_ranked.load();
-    const bool rkk = rk && (opt_rk == 1 || opt_rk == 3) && pi && P.lds_mode && L_HIST && P.hv16 && P.mv16 && !fold && !wide &&
+    const bool rkk = rk && (opt_rk == 1 || opt_rk == 3 || opt_rk == 4) && pi && P.lds_mode && L_HIST && P.hv16 && P.mv16 && !fold && !wide &&
                      !L_vcnt && (L_met == 1 || L_met == 2) && P.ncopies > 1 && P.cstride > LK * W && !P.kstart && !P.hord && hc &&
                      pl.interval > 0 && pl.interval < (1ll << 32) && hc->zspan < pl.interval && !dyn_claim_on();
+    // the widths that kernel is asked for (a product that does not fit the budget leaves its stream at the wider one)
+    const int rk_rw = opt_rk == 3 ? 2 : 1;
+    const int rk_mw = rkk && opt_rk == 1 && (uint64_t)mc->vmax - (uint64_t)mc->vmin < 4096 ? 12 : 16;
     const int vk = (P.hv_f64 ? 1 : 0) | (P.mv_f64 ? 2 : 0) | (P.ord_src ? 8 : 0) | (P.ord16 ? 16 : 0) | (P.hv32 ? 32 : 0) |
                    (pi ? 64 : 0) | (m32 ? 128 : 0) | (P.mv16 ? 256 : 0) | (fold ? 512 : 0) | (P.raw_dense ? 1024 : 0) |
                    (P.runs1 ? 4096 : 0) | (P.hv16 ? 8192 : 0) | (P.ukey32 ? 16384 : 0) |
                    (P.ocnt_mode != OCNT_TERMS && P.ocnt_mode != OCNT_HIST ? 32768 : 0) | (P.rank_cells ? 65536 : 0);
     const uint64_t occ_key = ((uint64_t)lds << 24) | ((uint64_t)wide << 23) | ((uint64_t)vk << 8) | ((uint64_t)L_met << 4) |
-                             ((uint64_t)hk << 1) | (L_ORD ? 1 : 0) | (rkk ? (opt_rk == 1 ? 3ull : 2ull) << 62 : 0);
+                             ((uint64_t)hk << 1) | (L_ORD ? 1 : 0) | (rkk ? (rk_mw == 12 ? 3ull : rk_rw == 1 ? 2ull : 1ull) << 60 : 0);
     if (pl.occ_key != occ_key) {
-        pl.occ = std::max(1, rkk ? ranked_occupancy(L_met, opt_rk == 1 ? 1 : 2, lds) : collect_occupancy(L_ORD, hk, L_met, lds, vk, wide));
+        pl.occ = std::max(1, rkk ? ranked_occupancy(L_met, rk_rw, rk_mw, lds) : collect_occupancy(L_ORD, hk, L_met, lds, vk, wide));
         pl.occ_key = occ_key;
     }
     const uint32_t wg_per_cu = (uint32_t)pl.occ;
@@ -4041,8 +4053,10 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
     need_wide(false);
     // the ranked kernel's 8-bit ranks, built here on first use (outside the timed region, like the other products); over
     // the HBM budget, or while another thread builds them, this request streams the 16-bit ranks
-    const uint8_t* r8 = rkk && opt_rk == 1 ? ensure_rank8(p->ctx, rk, s, p->stream) : nullptr;
-    const int rk_width = r8 ? 1 : 2;
+    // (the 12-bit metric deltas likewise, beside rank8 only: without them this request streams d16)
+    const uint8_t* r8 = rkk && rk_rw == 1 ? ensure_rank8(p->ctx, rk, s, p->stream) : nullptr;
+    const void* m12 = r8 && rk_mw == 12 ? ensure_d12(p->ctx, mc, s, p->stream) : nullptr;
+    const int rk_width = r8 ? 1 : 2, met_width = m12 ? 12 : 16;
     HIPX(hipEventRecord(pl.e0, p->stream));
     if (fold && P.npred > 0) {  // (inside the timed region: part of the collect)
         uint64_t* bits = (uint64_t*)p->s_xbits.ensure(p->ctx, std::max<size_t>(s->n_pad / 64, 1) * 8);
@@ -4057,7 +4071,7 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
         require(!P.claim && P.zkey, ESGPU_ERR_DEVICE, "internal: ranked kernel without static ranges or zone keys");
         RankedParams R{};
         R.rank = r8 ? (const void*)r8 : (const void*)P.ord16;
-        R.mv16 = P.mv16;
+        R.mv = m12 ? m12 : (const void*)P.mv16;
         R.hv16 = P.hv16;
         R.hv16_base = P.hv16_base;
         R.hv8 = P.hv8;
@@ -4087,7 +4101,7 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
         R.n_docs = P.n_docs;
         R.n_blocks = P.n_blocks;
         R.blocks_per_wg = P.blocks_per_wg;
-        launch_ranked(R, L_met, rk_width, grid, lds, p->stream);
+        launch_ranked(R, L_met, rk_width, met_width, grid, lds, p->stream);
     } else {
         launch_collect(P, L_ORD, L_HIST, L_met, wide, grid, lds, p->stream);
     }
@@ -4096,6 +4110,7 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
     dd_fold();
     p->last_kernel = rkk ? 1 : 0;
     if (rkk && rk_width == 1) p->last_narrow += s->max_doc;  // (last_bytes counts the rank at the ordinals' 2 bytes)
+    if (rkk && met_width == 12) p->last_narrow += s->max_doc / 2;  // (and the metric at d16's: d12 is ceil(1.5 max_doc))
     p->last_bytes += bytes_per_doc * (uint64_t)s->max_doc + (d_accept ? ((uint64_t)s->max_doc + 7) / 8 : 0) +
                      (P.hv16 ? (((uint64_t)s->max_doc + kB16Docs - 1) >> kB16Shift) * 8 : 0);
     p->last_path = rk ? 10 : P.lds_mode ? (P.windowed ? 2 : 1) : 0;
@@ -4277,6 +4292,30 @@ static const uint8_t* ensure_rank8(esgpu_ctx* c, const TermRanks* rk, const esgp
     std::lock_guard<std::mutex> lk(c->mu);
     m->rank8 = std::move(b);
     return m->rank8.as<uint8_t>();
+}
+// the packed 12-bit metric deltas of the ranked kernel, built from the column's d16 (vmax - vmin < 4096: the caller's
+// gate) in the same way and on the same occasion as rank8, and kept with the column (over the budget: null, and the
+// kernel streams d16)
+static const void* ensure_d12(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st) {
+    DevColumn* m = const_cast<DevColumn*>(col);
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        if (m->d12_done) return m->d12.p;
+        m->d12_done = true;
+    }
+    DevBuf b;
+    try {
+        b.alloc(c, p12_bytes(s->n_pad));
+        launch_d12(col->d16.as<uint16_t>(), s->n_pad, b.p, st);
+        HIPX(hipGetLastError());
+        HIPX(hipStreamSynchronize(st));
+    } catch (const EsError& e) {
+        if (e.code != ESGPU_ERR_OOM) throw;
+        return nullptr;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    m->d12 = std::move(b);
+    return m->d12.p;
 }
 
 // the 4 most frequent ordinals among 64 evenly spaced runs of 4,096 docs, most frequent first (cached with the ordinal
@@ -4464,7 +4503,7 @@ static const DevColumn* ensure_value_counts(esgpu_ctx* c, const DevColumn* col, 
     require(most <= 65535u, ESGPU_ERR_UNSUPPORTED, "value_count over a field with more than 65,535 values in one doc runs on the CPU path");
     v->vmin = 0;
     v->vmax = (int64_t)most;
-    v->d16_done = v->d32_done = v->b16_done = v->hll32_done = true;  // (no other compact copy is ever built for it)
+    v->d16_done = v->d32_done = v->d12_done = v->b16_done = v->hll32_done = true;  // (no other compact copy is ever built for it)
     v->wide_released.store(true, std::memory_order_release);
     m->vc_view = std::move(v);
     return m->vc_view.get();

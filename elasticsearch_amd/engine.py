@@ -296,8 +296,9 @@ class Engine:
 
     def set_option(self, name, value):
         """Layout option of this context (esgpu_ctx_set_option): 'compact_columns' / 'packed_metric' / 'block_deltas' /
-        0 or 1; 'ranked_terms' 0..3 (2: path 10 on the generic collect kernel instead of the ranked kernel, 3: the ranked kernel
-        over the 16-bit ranks instead of the 8-bit ones);
+        0 or 1; 'ranked_terms' 0..4 (2: path 10 on the generic collect kernel instead of the ranked kernel, 3: the ranked kernel
+        over the 16-bit ranks instead of the 8-bit ones, 4: over the 8-bit ranks and the 16-bit metric deltas, never the
+        12-bit ones);
         'hll_floor' 0..8 (include/esgpu.h ESGPU_OPT_HLL_FLOOR); 'numeric_terms_max_distinct': the distinct values of a long field
         in one segment above which terms over it are refused (default 2^22)."""
         N.check(N.lib().esgpu_ctx_set_option(self._ptr, self.OPTIONS[name], int(value)))

@@ -92,6 +92,10 @@ int esgpu_device_count(int* count);
  *                              The ranked kernel streams each doc's frequency rank as one byte (the segment's rank8
  *                              product: min(rank, 255), built on the first such collect, +1 B per doc of HBM; over the
  *                              HBM budget it streams the 16-bit ranks instead); 3 keeps it on the 16-bit ranks.
+ *                              Beside the 8-bit ranks it streams a metric whose values span < 4096 at 12 bits per
+ *                              doc (the column's d12 product: the 16-bit deltas packed 8 to three words, built on the
+ *                              first such collect, +1.5 B per doc of HBM; over the budget it streams the 16-bit deltas
+ *                              instead); 4 keeps it on the 8-bit ranks and the 16-bit deltas.  Values 0..4.
  *                              Not read from the environment.
  * and one limit:
  *   ESGPU_OPT_NUMERIC_TERMS_MAX_DISTINCT: terms over a long / date field count by the segment's numeric ordinals; a
@@ -485,7 +489,8 @@ int esgpu_plan_last_collect_stats(const esgpu_plan* plan, double* kernel_ms, uin
  * where ESGPU_OPT_RANKED_TERMS = 1 and the shape allows). */
 int esgpu_plan_last_collect_kernel(const esgpu_plan* plan, int32_t* id);
 /* The bytes the last collect's kernels streamed, at the widths they read: esgpu_plan_last_collect_stats' figure, less
- * one byte per doc where the ranked kernel ran over the 8-bit ranks.  Equal to that figure on every other path. */
+ * one byte per doc where the ranked kernel ran over the 8-bit ranks, and less another max_doc / 2 bytes where it ran
+ * over the 12-bit metric deltas.  Equal to that figure on every other path. */
 int esgpu_plan_last_collect_read_bytes(const esgpu_plan* plan, uint64_t* bytes);
 /* Wall time of the last esgpu_plan_build and the part of it spent waiting on the plan's stream (gathers and copies of
  * the winners' cells); the rest is host assembly of the result blocks.  Milliseconds. */
