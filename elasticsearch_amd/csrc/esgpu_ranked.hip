@@ -38,6 +38,15 @@ __device__ __forceinline__ rk_params_c* rk_again() {
     asm volatile("" : "+s"(q));
     return q;
 }
+// Two statements that hold the block loop's loads and waits where the source puts them (profiles/ranked_waits/isa.md).
+// rk_pin: an empty statement the compiler moves no load across -- without it the reloads at the loop's bottom, which
+// the prologue ends with as well, are merged and sunk to the loop's head, and the prologue's loads are reordered.
+// rk_drain: a wait for every outstanding vector load, as the last statement of the per-doc body -- the wait insertion
+// then knows that body's own loads have landed, and the single-key body that follows it on the static path is entered
+// through a wait for its first buffer only, not through vmcnt(0).  (0x0F70: vmcnt 0, expcnt and lgkmcnt at their
+// maximum, that is not waited for.  A wait written as inline assembly is not seen by that pass.)
+__device__ __forceinline__ void rk_pin() { asm volatile(""); }
+__device__ __forceinline__ void rk_drain() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 constexpr uint32_t kRkDocs = 8;                       // docs per thread per load (one 16-byte load per column)
 constexpr uint32_t kRkStepDocs = kRkWG * kRkDocs;     // 4,096
 static_assert(kBlockDocs == 2 * kRkStepDocs, "a zone block is two buffers of 8 docs per thread");
@@ -302,7 +311,9 @@ __global__ __launch_bounds__(kRkWG, ESGPU_RK_WAVES) void ranked_kernel(RankedPar
     // their loads are non-temporal: they do not displace the grid, the zone keys and the rank table in L2 / MALL (north
     // star at 1B docs 0.730 -> 0.655 ms per step with them).  Loads are unconditional and no loaded register
     // is copied, as in collect_kernel.  The zone keys are
-    // read through zkey_view (scalar loads), a block ahead.
+    // read through zkey_view (scalar loads), a block ahead.  A block starts while its second buffer is in flight: the
+    // loads are issued in the order ra, ma, rb, mb here and in the loop (rk_pin keeps them there), so the first half waits
+    // with vmcnt(2) for ra and ma only, and the second half, behind the first buffer's reload, with vmcnt(2) for rb and mb.
     const zkey_pair_c* const zk = zkey_view(P.zkey);
     const uint32_t tid8 = threadIdx.x * kRkDocs;
     i64x2_t z = zk[__builtin_amdgcn_readfirstlane(b_begin)];
@@ -310,8 +321,10 @@ __global__ __launch_bounds__(kRkWG, ESGPU_RK_WAVES) void ranked_kernel(RankedPar
     rk_m8<MW> ma, mb;
     ra.load(P.rank, (size_t)b_begin * kBlockDocs + tid8);
     ma.load(P.mv, (size_t)b_begin * kBlockDocs + tid8);
+    rk_pin();
     rb.load(P.rank, (size_t)b_begin * kBlockDocs + kRkStepDocs + tid8);
     mb.load(P.mv, (size_t)b_begin * kBlockDocs + kRkStepDocs + tid8);
+    rk_pin();
 #pragma unroll 1
     for (uint32_t cb = b_begin; cb < b_end; ++cb) {
         const int64_t kmn = z.x, kmx = z.y;
@@ -336,6 +349,7 @@ __global__ __launch_bounds__(kRkWG, ESGPU_RK_WAVES) void ranked_kernel(RankedPar
             slow_quad(d0 + 4u, ra.hi(), ma.pair(2), ma.pair(3), kmn, kmx);
             slow_quad(d0 + kRkStepDocs, rb.lo(), mb.pair(0), mb.pair(1), kmn, kmx);
             slow_quad(d0 + kRkStepDocs + 4u, rb.hi(), mb.pair(2), mb.pair(3), kmn, kmx);
+            rk_drain();
         }
         dirty = dirty || any;
         // each buffer has one reload per block, outside the branches: a reload under a branch gives the buffer two
@@ -359,6 +373,7 @@ __global__ __launch_bounds__(kRkWG, ESGPU_RK_WAVES) void ranked_kernel(RankedPar
         }
         rb.load(P.rank, nd1);
         mb.load(P.mv, nd1);
+        rk_pin();
     }
     if (dirty) flush();
 }

@@ -3999,6 +3999,9 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
     }();
     const uint32_t min_bpw = std::min<uint32_t>(L_ORD ? ord_min_bpw : hist_min_bpw, (P.n_blocks + slots - 1) / slots);
     P.blocks_per_wg = std::max(std::max(1u, bpw), min_bpw);
+    // tests only: ESGPU_DEBUG_BPW = n > 0 gives every workgroup n zone blocks, so that segments of a few blocks walk
+    // the kernels' block-to-block carry (read at each collect; the packed fields are checked against it below)
+    if (const char* e = std::getenv("ESGPU_DEBUG_BPW"); e && std::atoi(e) > 0) P.blocks_per_wg = (uint32_t)std::atoi(e);
     if (pi && P.lds_mode && !pi_fits(P.blocks_per_wg)) {  // a packed field could overflow: the f64 cells instead
         pi = false;
         P.mv32 = nullptr;
