@@ -71,7 +71,7 @@ struct esgpu_ctx {
     std::mutex mu;
     // layout options (esgpu_ctx_set_option): compact columns, packed integer metric cells
     std::atomic<int> opt_compact{1}, opt_pi{1}, opt_hll_fs{1}, opt_b16{1};
-    std::atomic<int> opt_ranked{1};  // ranked terms (ESGPU_OPT_RANKED_TERMS)
+    std::atomic<int> opt_ranked{5};  // ranked terms (ESGPU_OPT_RANKED_TERMS)
     // distinct values of a long column in one segment above which terms over it are refused (numeric ordinals)
     std::atomic<int64_t> opt_num_max{1ll << 22};
     // synthetic tables (device copies)

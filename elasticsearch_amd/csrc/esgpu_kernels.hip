@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "es_common.hpp"
+#include "es_group12.hpp"
 #include "es_pack12.hpp"
 #include "esgpu_kernels.hpp"
 
@@ -1744,6 +1745,64 @@ __global__ void d12_kernel(const uint16_t* src, uint32_t n8, uint32_t* out) {
 void launch_d12(const uint16_t* d16, uint32_t n, void* out, hipStream_t st) {
     const uint32_t n8 = n / kP12Group;
     if (n8) hipLaunchKernelGGL(d12_kernel, dim3(std::min<uint32_t>(8192, (n8 + 255) / 256)), dim3(256), 0, st, d16, n8, (uint32_t*)out);
+}
+// g12 (TermRanks, es_group12.hpp): one workgroup per zone block.  The block's docs are counted by group in LDS, the
+// counts scanned into the block's offsets, the deltas scattered by group into a staging block in LDS (the order inside a
+// group is whatever the cursor atomics give: the layout promises none) and the staged block packed and written in
+// order.  Docs at or past n_docs are pad docs: group kG12Groups, and their columns are not read.
+constexpr uint32_t kG12WG = 512;
+constexpr uint32_t kG12PerThread = kG12Block / kG12WG;
+static_assert(kG12Block == kBlockDocs && kG12Block % (kG12WG * kP12Group) == 0, "a g12 block is a zone block");
+__global__ __launch_bounds__(kG12WG) void g12_kernel(const uint16_t* __restrict__ rank16, const uint16_t* __restrict__ d16,
+                                                     uint32_t n_docs, uint32_t* __restrict__ out, uint16_t* __restrict__ off,
+                                                     unsigned long long* __restrict__ tot8) {
+    __shared__ uint32_t cursor[kG12Offs];
+    __shared__ uint16_t staged[kG12Block];
+    const uint32_t b = blockIdx.x;
+    for (uint32_t g = threadIdx.x; g < kG12Offs; g += kG12WG) cursor[g] = 0;
+    __syncthreads();
+    uint32_t grp[kG12PerThread], dv[kG12PerThread];
+#pragma unroll
+    for (uint32_t k = 0; k < kG12PerThread; ++k) {
+        const uint64_t doc = (uint64_t)b * kG12Block + k * kG12WG + threadIdx.x;
+        const bool in = doc < n_docs;
+        grp[k] = in ? g12_group(rank16[doc]) : kG12Groups;
+        dv[k] = in ? d16[doc] & kP12Mask : 0u;
+        atomicAdd(&cursor[grp[k]], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {  // (129 counts into their exclusive prefix sums: not worth a parallel scan)
+        uint32_t acc = 0;
+        for (uint32_t g = 0; g < kG12Offs; ++g) {
+            const uint32_t c = cursor[g];
+            cursor[g] = acc;
+            acc += c;
+        }
+    }
+    __syncthreads();
+    for (uint32_t g = threadIdx.x; g < kG12OffStride; g += kG12WG) {
+        const uint32_t o = g < kG12Offs ? cursor[g] : 0u;
+        off[(size_t)b * kG12OffStride + g] = (uint16_t)o;
+        if (g < kG12Offs && o) atomicAdd(&tot8[g], (unsigned long long)g12_ceil8(o));
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < kG12PerThread; ++k) staged[atomicAdd(&cursor[grp[k]], 1u)] = (uint16_t)dv[k];
+    __syncthreads();
+    for (uint32_t g = threadIdx.x; g < kG12Block / kP12Group; g += kG12WG) {
+        uint32_t d[8], w[3];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) d[j] = staged[g * kP12Group + j];
+        p12_pack8(d, w);
+        uint32_t* const o = out + ((size_t)b * (kG12Block / kP12Group) + g) * kP12Words;
+        o[0] = w[0];
+        o[1] = w[1];
+        o[2] = w[2];
+    }
+}
+void launch_g12(const uint16_t* rank16, const uint16_t* d16, uint32_t n_docs, uint32_t n_blocks, void* out, uint16_t* off,
+                unsigned long long* tot8, hipStream_t st) {
+    if (n_blocks) hipLaunchKernelGGL(g12_kernel, dim3(n_blocks), dim3(kG12WG), 0, st, rank16, d16, n_docs, (uint32_t*)out, off, tot8);
 }
 __global__ void delta32_kernel(const int64_t* v, uint32_t n, int64_t base, uint32_t* out) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)

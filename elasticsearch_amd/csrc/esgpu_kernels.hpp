@@ -184,6 +184,10 @@ struct RankedParams {
     uint32_t T_full, H, W, pk_shift, ncopies;
     uint32_t cstride;             // > K * W: cell K * W of every copy is spare
     uint32_t n_docs, n_blocks, blocks_per_wg;
+    // the grouped form only (esgpu_ranked_grouped.hip; rank is then rank16 and mv d16, read by the per-doc body): the
+    // rank-grouped 12-bit deltas of es_group12.hpp and their per-block offsets
+    const void* g12;
+    const uint16_t* g12_off;
 };
 
 // The range collect (esgpu_range.hip, path 11): one pass over the range field and one metric field into the [R] cells
@@ -468,6 +472,9 @@ int collect_occupancy(bool ord, int hk, int met, size_t lds, int vk, bool wide =
 // 12: d12 -- with rw 1 only)
 void launch_ranked(const RankedParams& p, int met, int rw, int mw, uint32_t grid, size_t lds, hipStream_t s);
 int ranked_occupancy(int met, int rw, int mw, size_t lds);
+// the grouped form of that kernel (esgpu_ranked_grouped.hip): RankedParams.g12 / g12_off set, rank = rank16, mv = d16
+void launch_ranked_grouped(const RankedParams& p, int met, uint32_t grid, size_t lds, hipStream_t s);
+int ranked_grouped_occupancy(int met, size_t lds);
 // returns whether the group floors and snapshot are left as lower bounds of the registers (HllParams.snap_ok for the
 // request's next segment)
 bool launch_hll(const HllParams& p, uint32_t cus, hipStream_t s);
@@ -531,6 +538,11 @@ void launch_rank_ord16(const uint16_t* ord16, uint32_t n, const uint16_t* rank_o
 void launch_rank8(const uint16_t* rank16, uint32_t n, uint8_t* out, hipStream_t st);
 // d12: n (a multiple of 8) 16-bit deltas below 4096 into the packed 12-bit form of es_pack12.hpp (3 n / 2 bytes)
 void launch_d12(const uint16_t* d16, uint32_t n, void* out, hipStream_t st);
+// g12 (es_group12.hpp): the n_blocks zone blocks of a segment of n_docs docs, each block's 12-bit deltas (d16's, below
+// 4096) grouped by min(rank16, kG12Groups) into `out` (g12_data_bytes) with its offsets into `off` (g12_off_bytes); tot8
+// (kG12Offs zeroed u64): the sum over the blocks of ceil8(off[r]) for every r
+void launch_g12(const uint16_t* rank16, const uint16_t* d16, uint32_t n_docs, uint32_t n_blocks, void* out, uint16_t* off,
+                unsigned long long* tot8, hipStream_t st);
 // ---- numeric ordinals (esgpu_numord.hip): a long column's sorted distinct values and each doc's rank among them ----
 // `v` with `width` 8 is the upload-width column, 4 / 2 its d32 / d16 deltas over vmin; span = vmax - vmin; the bitmap
 // holds span / 64 + 1 zeroed 64-bit words.  Spans below kNumOrdLdsBits are marked in a per-workgroup LDS bitmap.

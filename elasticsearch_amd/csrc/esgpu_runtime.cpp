@@ -36,6 +36,7 @@
 
 #include "../../include/esgpu.h"
 #include "es_common.hpp"
+#include "es_group12.hpp"
 #include "es_pack12.hpp"
 #include "es_rounding.hpp"
 #include "es_term_rank.hpp"
@@ -91,9 +92,10 @@ extern "C" int esgpu_ctx_set_option(esgpu_ctx* c, int32_t option, int64_t value)
             c->opt_num_max = value;
             return;
         }
-        // (2: path 10 on the generic collect kernel, 3: the ranked kernel over rank16, 4: over rank8 and d16)
+        // (2: path 10 on the generic collect kernel, 3: the ranked kernel over rank16, 4: over rank8 and d16, 5: its
+        // grouped form over the rank-grouped 12-bit deltas)
         if (option == ESGPU_OPT_RANKED_TERMS) {
-            require(value >= 0 && value <= 4, ESGPU_ERR_INVALID, "ranked terms option must be 0..4");
+            require(value >= 0 && value <= 5, ESGPU_ERR_INVALID, "ranked terms option must be 0..5");
             c->opt_ranked = (int)value;
             return;
         }
@@ -322,8 +324,20 @@ struct HcStats;  // hot set + partition capacities of a high-cardinality ordinal
 // the 16-bit ordinals (the same 2 B per doc).  rank8 is what the ranked kernel (esgpu_ranked.hip) streams instead: the
 // rank saturated to a byte -- the kernel only asks rank < K with K <= kRankedMax = 128 -- built from rank16 the first
 // time a collect decides on that kernel (ensure_rank8: +1 B per doc of HBM, only for segments that reach it)
+// g12 (es_group12.hpp, ensure_g12): the 12-bit deltas of one metric column with the docs of every zone block grouped by
+// the rank of their term -- what the grouped ranked kernel (esgpu_ranked_grouped.hip) streams in place of rank8 and d12:
+// 1.5 B per doc of the padded segment plus kG12OffBytes per block.  tot8: over all blocks the sum of ceil8(off[r]), the
+// positions a collect of the ranks below r reads (kept on the host: the request's byte count asks no device).
+struct DevColumn;
+struct G12Product {
+    const DevColumn* col = nullptr;  // the metric column it was made from (of the same segment as the ranks)
+    DevBuf data, off;
+    uint64_t tot8[kG12Offs] = {};
+    bool ready = false;  // published (not ready: being built on another thread, or over the HBM budget)
+};
 struct TermRanks {
     uint32_t T = 0;
+    std::vector<std::unique_ptr<G12Product>> g12;  // one entry per metric column asked for, under the context lock
     DevBuf counts;       // u64 [T]: doc count of every ordinal
     DevBuf ord_of_rank;  // u32 [T]
     DevBuf rank16;       // u16 [n_pad]: rank of the doc's ordinal, 0xFFFF missing
@@ -1223,7 +1237,10 @@ struct esgpu_plan {
     double last_ms = 0;
     uint64_t last_bytes = 0;
     uint64_t last_narrow = 0;  // bytes of last_bytes the kernel did not stream: a column read narrower than the layout counts it
-    int32_t last_kernel = 0;  // the last collect's LDS-window kernel: 0 collect_kernel, 1 ranked_kernel (esgpu_ranked.hip)
+    uint64_t last_extra = 0;   // bytes the kernel streamed that the layout does not count (the grouped form's product)
+    // the last collect's LDS-window kernel: 0 collect_kernel, 1 ranked_kernel (esgpu_ranked.hip), 2 its grouped form
+    // (esgpu_ranked_grouped.hip)
+    int32_t last_kernel = 0;
     double b_wait = 0, b_total = 0;  // last build: stream waits / whole call (ms)
     bool b_trace = false;
     std::vector<std::pair<const char*, double>> b_marks;
@@ -1254,6 +1271,7 @@ struct esgpu_plan {
     uint32_t zu_n = 0;
     uint8_t zu_w[kZuSlots] = {};  // ... and the timestamp bytes per doc of each launch (2: block deltas, 4: 32-bit deltas)
     uint32_t zu_g[kZuSlots] = {};  // ... and its zone-keys workgroups (words written)
+    uint8_t zu_nw[kZuSlots] = {};  // ... and the bytes per doc of those blocks that count as last_narrow (grouped form: 4)
     DevBuf d_claim;            // collect kernel's chunk-claim counter pair (zeroed once; every launch leaves it zero)
     Scratch s_hcur, s_hused, s_hslab;  // hot/cold counting: overflow cursors, static-region fills, hot slabs
     PinnedBuf h_hcerr;         // hot/cold counting: capacity-violation word (written by the scatter kernel)
@@ -1952,6 +1970,8 @@ static uint32_t pi_copies(int met);
 // ranked terms: the largest shard_size collected over ranks (K x W cells in LDS) -- covers the default shard_size of a
 // size-10 request over 10 or more shards (size x min(10, shards) = 100)
 constexpr uint32_t kRankedMax = 128;
+constexpr uint32_t kG12MaxK = 16;  // ranks up to which ESGPU_OPT_RANKED_TERMS = 5 takes the grouped form (collect_grid_cells)
+static_assert(kRankedMax == kG12Groups && kBlockDocs == kG12Block, "es_group12.hpp groups the ranks a request can collect");
 static uint32_t ranked_window();
 static uint32_t ranked_copies();
 static void clear_grid(esgpu_plan* p, Pipeline& pl);
@@ -1961,6 +1981,7 @@ static const TermRanks* ensure_term_ranks(esgpu_ctx* c, const DevColumn* col, co
 static bool ranked_terms_on(const esgpu_ctx* c);
 static const uint8_t* ensure_rank8(esgpu_ctx* c, const TermRanks* rk, const esgpu_segment* s, hipStream_t st);
 static const void* ensure_d12(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
+static const G12Product* ensure_g12(esgpu_ctx* c, const TermRanks* rk, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
 static const DevColumn* terms_col(esgpu_plan* p, const esgpu_segment* s, const std::string& field);
 static const DevColumn* value_count_metric(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s);
 static const uint32_t* ensure_d32(esgpu_ctx* c, const DevColumn* col, const esgpu_segment* s, hipStream_t st);
@@ -3951,22 +3972,34 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
     // the kernel sends the docs it does not collect).  Its per-doc body divides by the interval in 32 bits.
     // ESGPU_OPT_RANKED_TERMS = 2 keeps path 10 on collect_kernel; 3 keeps the ranked kernel on the 16-bit ranks, which 1
     // takes only when the segment's rank8 product does not fit the HBM budget; 4 keeps it on rank8 and d16, which 1 takes
-    // when the metric spans 4096 or more, or its d12 product does not fit.
+    // when the metric spans 4096 or more, or its d12 product does not fit.  5 is the grouped form of that kernel
+    // (esgpu_ranked_grouped.hip) over the rank-grouped 12-bit deltas of es_group12.hpp, for a metric spanning < 4096;
+    // where the product is not to be had (over the HBM budget, being built on another thread) or the metric spans more,
+    // the request runs exactly as under 1.
     const int opt_rk = p->ctx->opt_ranked.load();
-    const bool rkk = rk && (opt_rk == 1 || opt_rk == 3 || opt_rk == 4) && pi && P.lds_mode && L_HIST && P.hv16 && P.mv16 && !fold && !wide &&
+    const bool rkk = rk && (opt_rk == 1 || opt_rk == 3 || opt_rk == 4 || opt_rk == 5) && pi && P.lds_mode && L_HIST && P.hv16 && P.mv16 && !fold && !wide &&
                      !L_vcnt && (L_met == 1 || L_met == 2) && P.ncopies > 1 && P.cstride > LK * W && !P.kstart && !P.hord && hc &&
                      pl.interval > 0 && pl.interval < (1ll << 32) && hc->zspan < pl.interval && !dyn_claim_on();
     // the widths that kernel is asked for (a product that does not fit the budget leaves its stream at the wider one)
     const int rk_rw = opt_rk == 3 ? 2 : 1;
-    const int rk_mw = rkk && opt_rk == 1 && (uint64_t)mc->vmax - (uint64_t)mc->vmin < 4096 ? 12 : 16;
+    const int rk_mw = rkk && (opt_rk == 1 || opt_rk == 5) && (uint64_t)mc->vmax - (uint64_t)mc->vmin < 4096 ? 12 : 16;
+    // the grouped product, built here on first use (outside the timed region, like the other products): the launch
+    // geometry below depends on which kernel runs
+    // Measured: the grouped body pays where a wave's 512 positions meet an offset or two -- 10 ranks: the
+    // north star's step -31 % -- and loses where they meet many (20 / 40 / 80 ranks at 125M docs: kernel +8 / +5 / +29 %),
+    // so it is taken up to kG12MaxK ranks; above, the request runs as under 1.  (ESGPU_G12_MAX_K, read at each collect:
+    // tests and A/B runs move the bound.)
+    const char* const g12_env = std::getenv("ESGPU_G12_MAX_K");
+    const uint32_t g12_max_k = g12_env && std::atoi(g12_env) > 0 ? (uint32_t)std::atoi(g12_env) : kG12MaxK;
+    const G12Product* g12 = rkk && opt_rk == 5 && rk_mw == 12 && LK <= g12_max_k ? ensure_g12(p->ctx, rk, mc, s, p->stream) : nullptr;
     const int vk = (P.hv_f64 ? 1 : 0) | (P.mv_f64 ? 2 : 0) | (P.ord_src ? 8 : 0) | (P.ord16 ? 16 : 0) | (P.hv32 ? 32 : 0) |
                    (pi ? 64 : 0) | (m32 ? 128 : 0) | (P.mv16 ? 256 : 0) | (fold ? 512 : 0) | (P.raw_dense ? 1024 : 0) |
                    (P.runs1 ? 4096 : 0) | (P.hv16 ? 8192 : 0) | (P.ukey32 ? 16384 : 0) |
                    (P.ocnt_mode != OCNT_TERMS && P.ocnt_mode != OCNT_HIST ? 32768 : 0) | (P.rank_cells ? 65536 : 0);
     const uint64_t occ_key = ((uint64_t)lds << 24) | ((uint64_t)wide << 23) | ((uint64_t)vk << 8) | ((uint64_t)L_met << 4) |
-                             ((uint64_t)hk << 1) | (L_ORD ? 1 : 0) | (rkk ? (rk_mw == 12 ? 3ull : rk_rw == 1 ? 2ull : 1ull) << 60 : 0);
+                             ((uint64_t)hk << 1) | (L_ORD ? 1 : 0) | (rkk ? (g12 ? 4ull : rk_mw == 12 ? 3ull : rk_rw == 1 ? 2ull : 1ull) << 60 : 0);
     if (pl.occ_key != occ_key) {
-        pl.occ = std::max(1, rkk ? ranked_occupancy(L_met, rk_rw, rk_mw, lds) : collect_occupancy(L_ORD, hk, L_met, lds, vk, wide));
+        pl.occ = std::max(1, g12 ? ranked_grouped_occupancy(L_met, lds) : rkk ? ranked_occupancy(L_met, rk_rw, rk_mw, lds) : collect_occupancy(L_ORD, hk, L_met, lds, vk, wide));
         pl.occ_key = occ_key;
     }
     const uint32_t wg_per_cu = (uint32_t)pl.occ;
@@ -4050,6 +4083,7 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
         if (ud) {
             // (read by esgpu_plan_last_collect_stats: no per-collect copy to the host on the request's path)
             p->zu_w[p->zu_n] = P.hv16 ? (P.hv8_and ? 3 : 2) : 4;  // timestamp bytes per doc the skipped blocks did not read
+            p->zu_nw[p->zu_n] = g12 ? 4 : 0;  // the grouped form reads neither rank16 nor d16 of those blocks
             ++p->zu_n;
         }
     }
@@ -4057,7 +4091,8 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
     // the ranked kernel's 8-bit ranks, built here on first use (outside the timed region, like the other products); over
     // the HBM budget, or while another thread builds them, this request streams the 16-bit ranks
     // (the 12-bit metric deltas likewise, beside rank8 only: without them this request streams d16)
-    const uint8_t* r8 = rkk && rk_rw == 1 ? ensure_rank8(p->ctx, rk, s, p->stream) : nullptr;
+    // (the grouped form needs neither)
+    const uint8_t* r8 = rkk && !g12 && rk_rw == 1 ? ensure_rank8(p->ctx, rk, s, p->stream) : nullptr;
     const void* m12 = r8 && rk_mw == 12 ? ensure_d12(p->ctx, mc, s, p->stream) : nullptr;
     const int rk_width = r8 ? 1 : 2, met_width = m12 ? 12 : 16;
     HIPX(hipEventRecord(pl.e0, p->stream));
@@ -4075,6 +4110,8 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
         RankedParams R{};
         R.rank = r8 ? (const void*)r8 : (const void*)P.ord16;
         R.mv = m12 ? m12 : (const void*)P.mv16;
+        R.g12 = g12 ? g12->data.p : nullptr;
+        R.g12_off = g12 ? g12->off.as<uint16_t>() : nullptr;
         R.hv16 = P.hv16;
         R.hv16_base = P.hv16_base;
         R.hv8 = P.hv8;
@@ -4104,16 +4141,21 @@ static int collect_grid_cells(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
         R.n_docs = P.n_docs;
         R.n_blocks = P.n_blocks;
         R.blocks_per_wg = P.blocks_per_wg;
-        launch_ranked(R, L_met, rk_width, met_width, grid, lds, p->stream);
+        if (g12) launch_ranked_grouped(R, L_met, grid, lds, p->stream);
+        else launch_ranked(R, L_met, rk_width, met_width, grid, lds, p->stream);
     } else {
         launch_collect(P, L_ORD, L_HIST, L_met, wide, grid, lds, p->stream);
     }
     HIPX(hipGetLastError());
     HIPX(hipEventRecord(pl.e1, p->stream));
     dd_fold();
-    p->last_kernel = rkk ? 1 : 0;
-    if (rkk && rk_width == 1) p->last_narrow += s->max_doc;  // (last_bytes counts the rank at the ordinals' 2 bytes)
-    if (rkk && met_width == 12) p->last_narrow += s->max_doc / 2;  // (and the metric at d16's: d12 is ceil(1.5 max_doc))
+    p->last_kernel = g12 ? 2 : rkk ? 1 : 0;
+    // the grouped form streams, of every block, the groups of 8 that hold its positions below off[K], and its offsets;
+    // the blocks with several keys read their rank16 and d16 as the layout counts them, the others none of either
+    // (zu_nw: settled with the zone-skip counters)
+    if (g12) p->last_extra += g12_prefix_bytes(g12->tot8[P.T]) + g12_off_bytes(P.n_blocks);
+    if (rkk && !g12 && rk_width == 1) p->last_narrow += s->max_doc;  // (last_bytes counts the rank at the ordinals' 2 bytes)
+    if (rkk && !g12 && met_width == 12) p->last_narrow += s->max_doc / 2;  // (and the metric at d16's: d12 is ceil(1.5 max_doc))
     p->last_bytes += bytes_per_doc * (uint64_t)s->max_doc + (d_accept ? ((uint64_t)s->max_doc + 7) / 8 : 0) +
                      (P.hv16 ? (((uint64_t)s->max_doc + kB16Docs - 1) >> kB16Shift) * 8 : 0);
     p->last_path = rk ? 10 : P.lds_mode ? (P.windowed ? 2 : 1) : 0;
@@ -4319,6 +4361,47 @@ static const void* ensure_d12(esgpu_ctx* c, const DevColumn* col, const esgpu_se
     std::lock_guard<std::mutex> lk(c->mu);
     m->d12 = std::move(b);
     return m->d12.p;
+}
+// the rank-grouped 12-bit deltas of the grouped ranked kernel (es_group12.hpp), built from rank16 and the metric's d16
+// (vmax - vmin < 4096: the caller's gate) on the first collect that decides on that kernel for the pair, and kept with
+// the ranks, one entry per metric column (charged to the HBM budget: the data and the offsets; over the budget, or
+// while another thread builds it: null, and the request runs as ESGPU_OPT_RANKED_TERMS = 1 does)
+static const G12Product* ensure_g12(esgpu_ctx* c, const TermRanks* rk, const DevColumn* col, const esgpu_segment* s, hipStream_t st) {
+    TermRanks* m = const_cast<TermRanks*>(rk);
+    G12Product* e = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        for (const auto& x : m->g12)
+            if (x->col == col) return x->ready ? x.get() : nullptr;
+        m->g12.emplace_back(new G12Product());
+        e = m->g12.back().get();
+        e->col = col;
+    }
+    // (built outside the lock, published under it once the recode has finished)
+    const uint32_t n_blocks = s->n_pad / kBlockDocs;
+    DevBuf data, off;
+    uint64_t tot8[kG12Offs] = {};
+    try {
+        DevBuf tot;
+        data.alloc(c, g12_data_bytes(n_blocks));
+        off.alloc(c, g12_off_bytes(n_blocks));
+        tot.alloc(c, sizeof tot8);
+        HIPX(hipMemsetAsync(tot.p, 0, sizeof tot8, st));
+        launch_g12(rk->rank16.as<uint16_t>(), col->d16.as<uint16_t>(), s->max_doc, n_blocks, data.p, off.as<uint16_t>(),
+                   tot.as<unsigned long long>(), st);
+        HIPX(hipGetLastError());
+        HIPX(hipMemcpyAsync(tot8, tot.p, sizeof tot8, hipMemcpyDeviceToHost, st));
+        HIPX(hipStreamSynchronize(st));
+    } catch (const EsError& err) {
+        if (err.code != ESGPU_ERR_OOM) throw;
+        return nullptr;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    e->data = std::move(data);
+    e->off = std::move(off);
+    std::memcpy(e->tot8, tot8, sizeof tot8);
+    e->ready = true;
+    return e;
 }
 
 // the 4 most frequent ordinals among 64 evenly spaced runs of 4,096 docs, most frequent first (cached with the ordinal
@@ -4901,6 +4984,7 @@ extern "C" int esgpu_plan_collect_segment(esgpu_plan* p, const esgpu_segment* s,
         }
         p->last_bytes = 0;
         p->last_narrow = 0;
+        p->last_extra = 0;
         p->last_ms = -1;
         p->last_kernel = 0;
         p->zu_n = 0;
@@ -4978,6 +5062,7 @@ static void resolve_collect_stats(esgpu_plan* p) {
                 uint64_t w = 0;
                 for (uint32_t g = 0; g < p->zu_g[i]; ++g) w += ((const uint64_t*)p->zu_host.p)[(size_t)i * kZuMaxWG + g];
                 ud += w * p->zu_w[i];
+                p->last_narrow += w * p->zu_nw[i];
             }
             p->last_bytes -= std::min<uint64_t>(p->last_bytes, ud);
             p->zu_n = 0;
@@ -5000,7 +5085,7 @@ extern "C" int esgpu_plan_last_collect_read_bytes(const esgpu_plan* cp, uint64_t
         require(cp != nullptr && bytes != nullptr, ESGPU_ERR_INVALID, "null argument");
         esgpu_plan* p = const_cast<esgpu_plan*>(cp);
         resolve_collect_stats(p);
-        *bytes = p->last_bytes - std::min(p->last_bytes, p->last_narrow);
+        *bytes = p->last_bytes - std::min(p->last_bytes, p->last_narrow) + p->last_extra;
     });
 }
 

@@ -296,9 +296,10 @@ class Engine:
 
     def set_option(self, name, value):
         """Layout option of this context (esgpu_ctx_set_option): 'compact_columns' / 'packed_metric' / 'block_deltas' /
-        0 or 1; 'ranked_terms' 0..4 (2: path 10 on the generic collect kernel instead of the ranked kernel, 3: the ranked kernel
+        0 or 1; 'ranked_terms' 0..5 (2: path 10 on the generic collect kernel instead of the ranked kernel, 3: the ranked kernel
         over the 16-bit ranks instead of the 8-bit ones, 4: over the 8-bit ranks and the 16-bit metric deltas, never the
-        12-bit ones);
+        12-bit ones, 5 -- the default: its grouped form over the rank-grouped 12-bit deltas, which runs as 1 does where
+        the metric spans 4096 or more, more than 16 ranks are collected or the product does not fit the HBM budget);
         'hll_floor' 0..8 (include/esgpu.h ESGPU_OPT_HLL_FLOOR); 'numeric_terms_max_distinct': the distinct values of a long field
         in one segment above which terms over it are refused (default 2^22)."""
         N.check(N.lib().esgpu_ctx_set_option(self._ptr, self.OPTIONS[name], int(value)))

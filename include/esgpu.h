@@ -86,7 +86,7 @@ int esgpu_device_count(int* count);
  *   ESGPU_OPT_RANKED_TERMS:    an unfiltered top-level terms aggregation in count order over a shard's only segment
  *                              collects its sub-aggregations for the top shard_size terms alone, known beforehand from
  *                              the segment's term counts (the reference's breadth_first collect mode with the counting
- *                              pass cached per segment).  0 collects every term; 1 (the default) runs the
+ *                              pass cached per segment).  0 collects every term; 1 runs the
  *                              collect on the ranked kernel where the shape allows (stats / avg over 16-bit metric
  *                              deltas, block-delta keys of time-sorted data), 2 always on the generic collect kernel.
  *                              The ranked kernel streams each doc's frequency rank as one byte (the segment's rank8
@@ -95,7 +95,14 @@ int esgpu_device_count(int* count);
  *                              Beside the 8-bit ranks it streams a metric whose values span < 4096 at 12 bits per
  *                              doc (the column's d12 product: the 16-bit deltas packed 8 to three words, built on the
  *                              first such collect, +1.5 B per doc of HBM; over the budget it streams the 16-bit deltas
- *                              instead); 4 keeps it on the 8-bit ranks and the 16-bit deltas.  Values 0..4.
+ *                              instead); 4 keeps it on the 8-bit ranks and the 16-bit deltas.  5 (the default) runs
+ *                              the grouped form of that kernel where the metric spans < 4096 and the request collects
+ *                              at most 16 ranks (measured: the form loses at many ranks): it streams, of every
+ *                              zone block, only the 12-bit deltas of the docs it collects, from a product that stores
+ *                              each block's deltas grouped by rank (g12, built on the first such collect for the
+ *                              (terms field, metric field) pair: +1.5 B per doc and 260 B per block of HBM; neither
+ *                              rank8 nor d12 is built); where the metric spans more, more ranks are collected, or the
+ *                              product does not fit the budget, the request runs exactly as under 1.  Values 0..5.
  *                              Not read from the environment.
  * and one limit:
  *   ESGPU_OPT_NUMERIC_TERMS_MAX_DISTINCT: terms over a long / date field count by the segment's numeric ordinals; a
@@ -486,11 +493,13 @@ int esgpu_plan_destroy(esgpu_plan* plan);
 int esgpu_plan_last_collect_stats(const esgpu_plan* plan, double* kernel_ms, uint64_t* algorithmic_bytes,
                                   int32_t* path);
 /* The kernel that ran the last collect's LDS-window launch: 0 the generic collect kernel, 1 the ranked kernel (path 10
- * where ESGPU_OPT_RANKED_TERMS = 1 and the shape allows). */
+ * where ESGPU_OPT_RANKED_TERMS = 1, 3, 4 or 5 and the shape allows), 2 its grouped form (ESGPU_OPT_RANKED_TERMS = 5). */
 int esgpu_plan_last_collect_kernel(const esgpu_plan* plan, int32_t* id);
 /* The bytes the last collect's kernels streamed, at the widths they read: esgpu_plan_last_collect_stats' figure, less
  * one byte per doc where the ranked kernel ran over the 8-bit ranks, and less another max_doc / 2 bytes where it ran
- * over the 12-bit metric deltas.  Equal to that figure on every other path. */
+ * over the 12-bit metric deltas.  The grouped form: that figure less the 4 bytes per doc of rank and metric deltas in
+ * the zone blocks inside one key, plus what it streams in their place -- of every block the 12 bytes of each group of 8
+ * positions below off[K], and the block's 260 bytes of offsets.  Equal to that figure on every other path. */
 int esgpu_plan_last_collect_read_bytes(const esgpu_plan* plan, uint64_t* bytes);
 /* Wall time of the last esgpu_plan_build and the part of it spent waiting on the plan's stream (gathers and copies of
  * the winners' cells); the rest is host assembly of the result blocks.  Milliseconds. */
