@@ -344,7 +344,9 @@ class FilterBuilder(_Builder):
 
 class RangeBuilder(_Builder):
     """range aggregation (RangeAggregator / InternalRange): one bucket per [from, to) over a long, date or double field,
-    every range emitted, sorted by (from, to).  On the GPU path at the top level with numeric metric sub-aggregations."""
+    every range emitted, sorted by (from, to).  On the GPU path at the top level with numeric metric sub-aggregations
+    and with date_histogram sub-aggregations of numeric metrics (one histogram per range; over a single-valued range
+    field).  A numeric histogram, terms, filter, range, filters or cardinality child stays on the CPU path."""
     type = N.AGG_RANGE
 
     def __init__(self, name):
@@ -389,7 +391,9 @@ class FiltersBuilder(_Builder):
     request order, a doc in every bucket whose filter it matches, and optionally the "other" bucket of the docs matching
     none.  filter(key, query) adds a named filter (a repeated key replaces the query and keeps its position),
     filter(query) an anonymous one (keys "0", "1", ...); a query is a TermQuery, a RangeQuery or a list of them (their
-    conjunction; the empty list is match_all).  On the GPU path at the top level with numeric metric sub-aggregations."""
+    conjunction; the empty list is match_all).  On the GPU path at the top level with numeric metric sub-aggregations
+    and with date_histogram sub-aggregations of numeric metrics (one histogram per bucket, the other bucket included).
+    A numeric histogram, terms, filter, range, filters or cardinality child stays on the CPU path."""
     type = N.AGG_FILTERS
 
     def __init__(self, name):

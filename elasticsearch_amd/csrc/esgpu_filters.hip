@@ -11,62 +11,19 @@
 // accepted and matches no filter gets the other bucket's bit.  Values are compared as signed 64-bit keys: ordinals and
 // longs as they are, doubles through the order-preserving image of their bits (rg_key).
 //
-// Accumulation and flush: esgpu_range_cells.hpp (shared with the range collect).
-#include "esgpu_range_cells.hpp"
+// The tables and a clause column's lookup (FlTab, fl_column): esgpu_mask_docs.hpp, shared with the keyed form
+// (esgpu_mask_hist.hip); accumulation and flush: esgpu_range_cells.hpp, shared with the range collect too.  The staging
+// and the round below are also there as fl_stage / fl_docs for the keyed kernel; this kernel keeps them written out --
+// called through those functions its counts-only and avg instantiations took 74 VGPRs instead of 68 / 72 and lost a
+// wave per SIMD (DESIGN §5 "Path 13").
+#include "esgpu_mask_docs.hpp"
 
 namespace esgpu {
 
 struct FlLds {
-    long long cuts[kFilterCols][kRangeCuts];
-    unsigned long long masks[kFilterCols][kRangeCuts + 1];
-    unsigned long long no_value[kFilterCols];
-    FilterCol col[kFilterCols];
+    FlTab tab;
     RgCells cells;
 };
-
-// one clause column into the 8 masks of a thread's docs: every load unconditional (the columns and present bitsets are
-// allocated over whole zone blocks; what lies past n_docs is masked by the caller)
-__device__ __forceinline__ void fl_column(const FlLds& S, uint32_t c, const FilterCol& C, uint32_t base,
-                                          unsigned long long (&m)[kRgDocs]) {
-    const long long* cuts = S.cuts[c];
-    const unsigned long long* masks = S.masks[c];
-    const unsigned long long none = S.no_value[c];
-    const uint32_t n = C.n_cuts;
-    uint32_t step0 = 0;
-    if (n) step0 = 1u << (31 - __clz((int)n));
-    if (C.kind == FCOL_ORD) {
-#pragma unroll
-        for (uint32_t q = 0; q < kRgQuads; ++q) {
-            const uint32_t doc0 = base + q * kRgQuad + threadIdx.x * 4;
-            uint32_t o[4];
-            load_u32x4((const uint32_t*)C.v, doc0, o);
-            const uint32_t pr = C.present ? bits4(C.present, doc0) : 0xFu;
-#pragma unroll
-            for (uint32_t t = 0; t < 4; ++t) {
-                const bool has = ((pr >> t) & 1u) && o[t] != kMissingOrd;
-                const unsigned long long vm = rg_lookup(cuts, masks, n, step0, (long long)o[t]);
-                m[4 * q + t] &= has ? vm : none;
-            }
-        }
-    } else {
-        const bool f64 = C.kind == FCOL_F64;
-#pragma unroll
-        for (uint32_t q = 0; q < kRgQuads; ++q) {
-            const uint32_t doc0 = base + q * kRgQuad + threadIdx.x * 4;
-            long long v[4];
-            load_i64x4((const int64_t*)C.v, doc0, (int64_t*)v);
-            const uint32_t pr = C.present ? bits4(C.present, doc0) : 0xFu;
-#pragma unroll
-            for (uint32_t t = 0; t < 4; ++t) {
-                const double d = bits_dbl((unsigned long long)v[t]);
-                const bool has = ((pr >> t) & 1u) && !(f64 && d != d);  // NaN satisfies no comparison
-                const long long key = f64 ? rg_key((unsigned long long)v[t]) : v[t];
-                const unsigned long long vm = rg_lookup(cuts, masks, n, step0, key);
-                m[4 * q + t] &= has ? vm : none;
-            }
-        }
-    }
-}
 
 template <int MET>
 __global__ __launch_bounds__(kRgWG) void filters_kernel(FiltersParams P) {
@@ -77,11 +34,11 @@ __global__ __launch_bounds__(kRgWG) void filters_kernel(FiltersParams P) {
         if (c >= P.n_cols) break;
         const uint64_t* tab = P.table + (size_t)c * kFilterStride;
         const uint32_t n = P.col[c].n_cuts;
-        for (uint32_t i = threadIdx.x; i < n; i += kRgWG) S.cuts[c][i] = (long long)tab[i];
-        for (uint32_t i = threadIdx.x; i <= n; i += kRgWG) S.masks[c][i] = tab[kRangeCuts + i];
+        for (uint32_t i = threadIdx.x; i < n; i += kRgWG) S.tab.cuts[c][i] = (long long)tab[i];
+        for (uint32_t i = threadIdx.x; i <= n; i += kRgWG) S.tab.masks[c][i] = tab[kRangeCuts + i];
         if (threadIdx.x == 0) {
-            S.no_value[c] = tab[2 * kRangeCuts + 1];
-            S.col[c] = P.col[c];
+            S.tab.no_value[c] = tab[2 * kRangeCuts + 1];
+            S.tab.col[c] = P.col[c];
         }
     }
     rg_cells_init(S.cells);
@@ -110,17 +67,13 @@ __global__ __launch_bounds__(kRgWG) void filters_kernel(FiltersParams P) {
         }
 #pragma unroll
         for (uint32_t j = 0; j < kRgDocs; ++j) m[j] = P.all_mask;
-        // the clause columns one after another: a rolled loop (the descriptors in LDS), so that one column's values are
-        // live at a time
 #pragma unroll 1
-        for (uint32_t c = 0; c < P.n_cols; ++c) fl_column(S, c, S.col[c], base, m);
+        for (uint32_t c = 0; c < P.n_cols; ++c) fl_column(S.tab, c, S.tab.col[c], base, m);
 #pragma unroll
         for (uint32_t j = 0; j < kRgDocs; ++j) {
             const bool in = (ok >> j) & 1u;
             m[j] = in ? (m[j] ? m[j] : other) : 0ull;
         }
-        // the metric column after the clause columns: its 8 values are not live while the masks are made (loaded before
-        // them, MET 1 / 2 took 86 VGPRs, 5 waves per SIMD, against 72 / 80 and 7 / 6 this way)
         if constexpr (MET > 0) {
 #pragma unroll
             for (uint32_t q = 0; q < kRgQuads; ++q) {

@@ -259,6 +259,28 @@ struct FiltersParams {
 void launch_filters(const FiltersParams& p, int met, uint32_t grid, hipStream_t s);
 int filters_occupancy(int met);
 
+// The keyed mask collect (esgpu_mask_hist.hip, path 13): a date_histogram under a range or a filters aggregation.  The
+// doc masks come from a RangeParams (single-valued range field) or a FiltersParams as above, whose grid pointers name the
+// pipeline's [H][R] grid (cell = key row * R + bucket); HistKeys adds the key dimension: the timestamp column, its
+// per-block key rows (launch_zone_keys over the same rounding: zkey rows are grid rows) and the rounding itself for the
+// blocks that span several keys.  A doc of a bucket counts in g_ocnt[bucket] whether it has a timestamp or not.
+struct HistKeys {
+    const int64_t* hv;           // the timestamps, single-valued longs, 8 bytes per doc (null: the segment has none)
+    const uint64_t* hv_present;  // null = dense
+    const int64_t* zkey;         // per zone block (kmn, kmx), (1, 0) for a block without a value
+    int64_t interval, offset, key0;  // affine roundings: row = floor((v - offset) / interval) - key0
+    const int64_t* kstart;       // table roundings: step start instants [nsteps] (row = slot of the last start <= v)
+    const uint32_t* kslot;       // row of each step (null: step j is row j)
+    uint32_t nsteps;
+    uint32_t H;                  // grid rows
+    uint32_t mg_m, mg_s1, mg_s2; // magic division by interval ...
+    uint32_t keys32;             // ... for blocks of at most this many keys (keys x interval < 2^32; 0: never)
+    unsigned long long* g_ocnt;  // [R] doc counts of the buckets
+};
+void launch_mask_hist(const RangeParams& p, const HistKeys& k, int met, uint32_t grid, hipStream_t s);
+void launch_mask_hist(const FiltersParams& p, const HistKeys& k, int met, uint32_t grid, hipStream_t s);
+int mask_hist_occupancy(int met, bool filters);
+
 enum HllKind : int32_t { HLL_I64 = 0, HLL_F64 = 1, HLL_ORD = 2 };
 
 struct HllParams {

@@ -8,34 +8,22 @@
 // a long column against long cuts (the host made each the least long whose double reaches the bound), a double column
 // through the order-preserving image of its bits (rg_key; NaN and +Infinity belong to no range).
 //
-// Accumulation and flush: esgpu_range_cells.hpp (shared with the filters collect).
-#include "esgpu_range_cells.hpp"
+// The tables and the single-valued round: esgpu_mask_docs.hpp (shared with the keyed form, esgpu_mask_hist.hip);
+// accumulation and flush: esgpu_range_cells.hpp (shared with the filters collect too).
+#include "esgpu_mask_docs.hpp"
 
 namespace esgpu {
 
 struct RgLds {
-    long long cuts[kRangeCuts];
-    unsigned long long masks[kRangeCuts + 1];
+    RgTab tab;
     RgCells cells;
 };
-
-// a value's mask (rg_key puts -0.0 just below +0.0: the host's cut for a bound of 0.0 is the key of -0.0)
-template <bool F64>
-__device__ __forceinline__ unsigned long long rg_value_mask(const RgLds& S, uint32_t n, uint32_t step0, unsigned long long bits) {
-    if (F64) {
-        const double d = bits_dbl(bits);
-        if (!(d < INFINITY)) return 0ull;  // NaN >= from and +Infinity < to are false for every range
-        return rg_lookup(S.cuts, S.masks, n, step0, rg_key(bits));
-    }
-    return rg_lookup(S.cuts, S.masks, n, step0, (long long)bits);
-}
 
 template <int MET, bool MULTI>
 __global__ __launch_bounds__(kRgWG) void range_kernel(RangeParams P) {
     __shared__ RgLds S;
     const uint32_t n = P.n_cuts, R = P.R;
-    for (uint32_t i = threadIdx.x; i < n; i += kRgWG) S.cuts[i] = (long long)P.table[i];
-    for (uint32_t i = threadIdx.x; i <= n; i += kRgWG) S.masks[i] = P.table[kRangeCuts + i];
+    rg_stage(S.tab, P.table, n);
     rg_cells_init(S.cells);
     __syncthreads();
     uint32_t step0 = 0;
@@ -52,30 +40,7 @@ __global__ __launch_bounds__(kRgWG) void range_kernel(RangeParams P) {
         double x[kRgDocs];
         uint32_t mp = 0;  // bit j: doc j has a metric value
         if constexpr (!MULTI) {
-            // single-valued range field: 4 consecutive docs per quad, every column by 16-byte loads (the columns, present
-            // bitsets and the doc bitset are allocated over whole zone blocks; what lies past n_docs is masked below)
-            long long rv[kRgDocs], mvv[kRgDocs];
-            uint32_t ok = 0;
-#pragma unroll
-            for (uint32_t q = 0; q < kRgQuads; ++q) {
-                const uint32_t doc0 = base + q * kRgQuad + threadIdx.x * 4;
-                load_i64x4((const int64_t*)P.rv, doc0, (int64_t*)&rv[4 * q]);
-                if constexpr (MET > 0) load_i64x4((const int64_t*)P.mv, doc0, (int64_t*)&mvv[4 * q]);
-                uint32_t o = 0xFu;
-                if (P.accept) o &= bits4(P.accept, doc0);
-                if (P.rv_present) o &= bits4(P.rv_present, doc0);
-                const uint32_t left = doc0 < P.n_docs ? P.n_docs - doc0 : 0u;
-                if (left < 4) o &= (1u << left) - 1u;
-                ok |= o << (4 * q);
-                if constexpr (MET > 0) mp |= (P.mv_present ? bits4(P.mv_present, doc0) : 0xFu) << (4 * q);
-            }
-#pragma unroll
-            for (uint32_t j = 0; j < kRgDocs; ++j) {
-                const unsigned long long vm = P.rv_f64 ? rg_value_mask<true>(S, n, step0, (unsigned long long)rv[j])
-                                                       : rg_value_mask<false>(S, n, step0, (unsigned long long)rv[j]);
-                m[j] = ((ok >> j) & 1u) ? vm : 0ull;
-                if constexpr (MET > 0) x[j] = P.mv_f64 ? bits_dbl((unsigned long long)mvv[j]) : (double)mvv[j];
-            }
+            rg_docs<MET>(S.tab, P, n, step0, base, m, x, mp);
         } else {
             // multi-valued range field (CSR): one doc per lane and sweep, its values in a loop
 #pragma unroll
@@ -89,7 +54,7 @@ __global__ __launch_bounds__(kRgWG) void range_kernel(RangeParams P) {
                 const uint64_t o1 = P.rv_off[d + 1];
                 unsigned long long acc = 0ull;
                 for (uint64_t o = P.rv_off[d]; o < o1; ++o)
-                    acc |= P.rv_f64 ? rg_value_mask<true>(S, n, step0, vals[o]) : rg_value_mask<false>(S, n, step0, vals[o]);
+                    acc |= P.rv_f64 ? rg_value_mask<true>(S.tab, n, step0, vals[o]) : rg_value_mask<false>(S.tab, n, step0, vals[o]);
                 m[j] = acc;
                 if constexpr (MET > 0) {
                     const long long raw = ((const long long*)P.mv)[d];

@@ -1068,7 +1068,9 @@ struct Pipeline {
     bool count_only = false;   // the filter aggregation's own doc_count (one cell, no metric)
     // a range aggregation's pipeline (collect path 11): the grid is [1][R] cells, one per range in bucket order, filled by
     // range_kernel from the range field and the pipeline's metric field; rtable: the device table of the ranges' cuts
-    // and masks (RangeParams.table) as made for a long (1) or a double (2) range column
+    // and masks (RangeParams.table) as made for a long (1) or a double (2) range column.  With a date_histogram child
+    // (hist_spec >= 0; collect path 13) the grid is [H][R], a row per histogram key, filled by mask_hist_kernel, and
+    // g_ocnt holds the R doc counts of the buckets (OCNT_TERMS); the same holds for a filters aggregation's pipeline
     bool range = false;
     std::string range_field;
     DevBuf d_rtable;
@@ -1346,12 +1348,12 @@ static int add_pipeline(esgpu_plan* p, int root, int fspec, int outer, int inner
     for (int b : {outer, inner}) {
         if (b < 0) continue;
         const SpecNode& n = p->specs[b];
-        if (n.s.type == ESGPU_AGG_RANGE) {  // (top level, metric leaves only: no inner dimension)
+        if (n.s.type == ESGPU_AGG_RANGE) {  // (top level; the inner dimension, if any, is a date_histogram: below)
             pl.range = true;
             pl.range_field = n.field;
             continue;
         }
-        if (n.s.type == ESGPU_AGG_FILTERS) {  // (top level, metric leaves only: no inner dimension)
+        if (n.s.type == ESGPU_AGG_FILTERS) {  // (top level, likewise)
             pl.filters = true;
             continue;
         }
@@ -1363,7 +1365,7 @@ static int add_pipeline(esgpu_plan* p, int root, int fspec, int outer, int inner
             pl.interval = 1;
             pl.offset = 0;
         } else if (n.s.type == ESGPU_AGG_TERMS) { pl.term_spec = b; pl.ord_field = n.field; }
-        else if (b == inner && outer >= 0 && p->specs[outer].s.type != ESGPU_AGG_TERMS) {
+        else if (b == inner && outer >= 0 && p->specs[outer].s.type != ESGPU_AGG_TERMS && !pl.range && !pl.filters) {
             // histogram under histogram: the inner histogram's key indices take the ordinal dimension of the grid
             pl.term_spec = b;
             pl.ord_field = n.field;
@@ -1477,12 +1479,25 @@ static Group compile_group(esgpu_plan* p, int r, int fspec) {
         // RangeAggregator / FiltersAggregator: its metric children grouped by field, one pipeline (one pass over the range field and that
         // metric field) each; every pipeline counts the ranges' docs alike and pipes[0]'s counts are the doc counts.  A
         // range without children gets one counting pipeline.
+        // A date_histogram child (collect path 13) gets pipelines of its own, one per metric field of its children, whose
+        // grids carry its keys as rows; they count the buckets' docs too (g_ocnt), so a root whose children are all
+        // date_histograms needs no counting pipeline.
+        std::vector<int> leaves;
+        for (int ch : root.children)
+            if (p->specs[ch].s.type != ESGPU_AGG_DATE_HISTOGRAM) leaves.push_back(ch);
         std::vector<LeafRef> refs;
-        g.pipes = add_leaf_pipelines(p, r, fspec, r, -1, root.children, &refs);
-        for (size_t j = 0; j < root.children.size(); ++j) {
+        if (!leaves.empty() || root.children.empty()) g.pipes = add_leaf_pipelines(p, r, fspec, r, -1, leaves, &refs);
+        size_t li = 0;
+        for (int ch : root.children) {
             ChildSrc cs;
-            cs.spec = root.children[j];
-            cs.leaf = refs[j];
+            cs.spec = ch;
+            if (p->specs[ch].s.type == ESGPU_AGG_DATE_HISTOGRAM) {
+                cs.bucket = true;
+                cs.pipes = add_leaf_pipelines(p, r, fspec, r, ch, p->specs[ch].children, &cs.grand);
+                for (int pi : cs.pipes) g.pipes.push_back(pi);
+            } else {
+                cs.leaf = refs[li++];
+            }
             g.kids.push_back(std::move(cs));
         }
         return g;
@@ -1662,10 +1677,20 @@ extern "C" int esgpu_plan_create(esgpu_ctx* c, const esgpu_agg_spec* specs, int3
                 const int pt = p->specs[n.s.parent].s.type;
                 require(is_bucket(pt) || pt == ESGPU_AGG_FILTER || pt == ESGPU_AGG_RANGE || pt == ESGPU_AGG_FILTERS, ESGPU_ERR_INVALID,
                         "metrics aggregations cannot have sub-aggregations");
-                require(pt != ESGPU_AGG_FILTERS || is_metric(n.s.type), ESGPU_ERR_UNSUPPORTED,
-                        "a filters aggregation with a bucket, filter or cardinality sub-aggregation runs on the CPU path");
-                require(pt != ESGPU_AGG_RANGE || is_metric(n.s.type), ESGPU_ERR_UNSUPPORTED,
-                        "a range aggregation with a bucket, filter or cardinality sub-aggregation runs on the CPU path");
+                // under a filters or a range aggregation: numeric metrics, and date_histograms of numeric metrics (collect
+                // path 13; by spec type -- the numeric histogram is not admitted)
+                require(pt != ESGPU_AGG_FILTERS || is_metric(n.s.type) || n.s.type == ESGPU_AGG_DATE_HISTOGRAM, ESGPU_ERR_UNSUPPORTED,
+                        "a filters aggregation with a bucket other than a date_histogram, a filter or a cardinality sub-aggregation "
+                        "runs on the CPU path");
+                require(pt != ESGPU_AGG_RANGE || is_metric(n.s.type) || n.s.type == ESGPU_AGG_DATE_HISTOGRAM, ESGPU_ERR_UNSUPPORTED,
+                        "a range aggregation with a bucket other than a date_histogram, a filter or a cardinality sub-aggregation "
+                        "runs on the CPU path");
+                if (pt == ESGPU_AGG_DATE_HISTOGRAM && p->specs[n.s.parent].s.parent >= 0) {
+                    const int gt = p->specs[p->specs[n.s.parent].s.parent].s.type;
+                    require((gt != ESGPU_AGG_FILTERS && gt != ESGPU_AGG_RANGE) || is_metric(n.s.type), ESGPU_ERR_UNSUPPORTED,
+                            "a date_histogram under a filters or a range aggregation with a bucket, filter or cardinality "
+                            "sub-aggregation runs on the CPU path");
+                }
                 p->specs[n.s.parent].children.push_back(i);
             }
             if (n.s.type == ESGPU_AGG_TERMS) {
@@ -3164,7 +3189,9 @@ static void build_range_table(const std::vector<RangeBucket>& rb, bool f64, std:
 
 // ---- what the range collect (path 11) and the filters collect (path 12) share on the host ----------------------------
 // Both fill a pipeline's [1][R] grid -- one cell per bucket, a doc's buckets a u64 mask -- from their own source of the
-// mask and the pipeline's metric field; RangeParams and FiltersParams name the fields of that part alike.
+// mask and the pipeline's metric field; RangeParams and FiltersParams name the fields of that part alike.  With a
+// date_histogram child (pl.hist_spec >= 0, path 13) the grid is [H][R], a row per key, and mask_hist_kernel fills it from
+// the same parameters plus HistKeys.
 
 // the pipeline's metric column in this segment (null: counts only, or an unmapped field, which collects nothing)
 static const DevColumn* mask_metric_column(const Pipeline& pl, const esgpu_segment* s, const char* under) {
@@ -3177,16 +3204,155 @@ static const DevColumn* mask_metric_column(const Pipeline& pl, const esgpu_segme
     return mc;
 }
 
-// The grid of R cells for this segment (allocated at a request's first segment; the value counts split from the doc
-// counts when the metric field turns sparse), the metric column, the doc range, the grid pointers and the compensated
-// sums into P; the metric column's bytes into *bytes.  Returns the kernel's MET.
+// the timestamp column of a path-13 pipeline in this segment (null: the segment lacks the field -- its docs count in
+// their buckets and in no histogram bucket)
+static const DevColumn* mask_hist_column(const Pipeline& pl, const esgpu_segment* s) {
+    const DevColumn* hc = s->col(pl.hist_field.c_str());
+    if (hc)
+        require(hc->type == ESGPU_COL_I64 && !hc->multi, ESGPU_ERR_UNSUPPORTED,
+                "a date_histogram under a range or a filters aggregation over a field that is not a single-valued long runs on "
+                "the CPU path");
+    return hc;
+}
+
+// The [H][R] grid of a path-13 pipeline for this segment: the key range from the timestamp column's vmin / vmax through
+// the request's rounding (the key table of a calendar / DST rounding included), as collect_grid_cells shapes a histogram
+// dimension -- allocated at a request's first segment, grown on either side when a later segment widens the range, its
+// single placeholder row re-shaped when the earlier segments had no timestamp.  The buckets' doc counts are counted
+// beside the cells (OCNT_TERMS: g_ocnt [R]).
+static void mask_hist_shape(esgpu_plan* p, Pipeline& pl, const DevColumn* hc, uint32_t R, bool sparse_metric) {
+    if (pl.fresh) {
+        pl.kt_lo = 0;
+        pl.kt_hi = -1;
+        pl.kt_start.clear();
+        pl.kt_key.clear();
+        pl.kt_slot.clear();
+    }
+    int64_t kmin = 0, kmax = 0, table_shift = 0;
+    bool has_keys = false;
+    const uint32_t H_before = pl.H;
+    if (hc && hc->vmin <= hc->vmax) {
+        if (pl.ktable) {
+            table_shift = build_key_table(p, pl, hc->vmin, hc->vmax);
+            kmax = (int64_t)pl.kt_key.size() - 1;
+        } else {
+            kmin = floor_div64(hc->vmin - pl.offset, pl.interval);
+            kmax = floor_div64(hc->vmax - pl.offset, pl.interval);
+        }
+        has_keys = true;
+    }
+    auto fits = [&](int64_t rows) {
+        require(rows <= 64 * 1024 * 1024, ESGPU_ERR_UNSUPPORTED, "histogram key range too large for a dense grid");
+        require((uint64_t)R * (uint64_t)rows <= (1ull << 31), ESGPU_ERR_UNSUPPORTED, "bucket grid too large");
+    };
+    if (!pl.allocated || pl.fresh) {
+        const int64_t rows = has_keys ? kmax - kmin + 1 : 1;
+        fits(rows);
+        const int64_t key0 = has_keys ? kmin : 0;
+        const int vcnt = sparse_metric ? 1 : 0;
+        const bool same = pl.allocated && pl.T == R && pl.H == (uint32_t)rows && pl.key0 == key0 && vcnt == pl.vcnt_mode &&
+                          pl.ocnt_mode == OCNT_TERMS;
+        pl.T = R;
+        pl.H = (uint32_t)rows;
+        pl.key0 = key0;
+        pl.vcnt_mode = vcnt;
+        pl.ocnt_mode = OCNT_TERMS;
+        pl.keyed = has_keys;
+        pl.value_count = R;
+        if (!same) alloc_grid(p, pl);
+        pl.fresh = false;
+        pl.dd = false;
+        pl.dd_vals = 0;
+        pl.dd_amax = 0;
+        return;
+    }
+    if (has_keys && !pl.keyed) {  // the earlier segments had no timestamp: their single placeholder row is empty
+        fits(kmax - kmin + 1);
+        pl.key0 = kmin;
+        regrid(p, pl, (uint32_t)(kmax - kmin + 1), 0);
+        pl.keyed = true;
+    } else if (has_keys && !pl.ktable) {
+        fits(std::max(pl.key0 + (int64_t)pl.H - 1, kmax) - std::min(pl.key0, kmin) + 1);
+        grow_keys(p, pl, kmin, kmax);
+    } else if (has_keys && ((uint32_t)pl.kt_key.size() != H_before || table_shift != 0)) {
+        fits((int64_t)pl.kt_key.size());
+        regrid(p, pl, (uint32_t)pl.kt_key.size(), table_shift);
+    }
+    if (sparse_metric && !pl.vcnt_mode) {
+        // the metric field turns sparse in this segment: the value counts split from the doc counts they equalled so far
+        const size_t cells = (size_t)pl.T * pl.H;
+        zero_counts(p, pl);
+        pl.g_vcnt.alloc(p->ctx, cells * 8);
+        HIPX(hipMemcpyAsync(pl.g_vcnt.p, pl.g_cnt.p, cells * 8, hipMemcpyDeviceToDevice, p->stream));
+        pl.vcnt_mode = 1;
+    }
+}
+
+// The key dimension of a path-13 launch: the timestamps, the rounding, and the blocks' key rows from the column's zone
+// maps (launch_zone_keys over the same rounding and key0, so a block's keys are grid rows).  The timestamps count 8 bytes
+// per doc; the docs of single-key blocks, whose timestamps the kernel does not read, come off again with the zone-skip
+// counters (esgpu_plan_last_collect_stats), and the zone-key words are added.
+static void mask_hist_keys(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, const DevColumn* hc, uint32_t n_blocks, HistKeys& K,
+                           uint64_t* bytes) {
+    K = HistKeys{};
+    K.H = pl.H;
+    K.g_ocnt = pl.g_ocnt.as<unsigned long long>();
+    K.interval = pl.interval;
+    K.offset = pl.offset;
+    K.key0 = pl.key0;
+    if (!hc || !(hc->vmin <= hc->vmax) || !pl.keyed) return;  // no timestamp in the segment
+    K.hv = (const int64_t*)wide_i64(p->ctx, hc, s, p->stream);  // (released upload-width values are rebuilt)
+    K.hv_present = hc->present.as<uint64_t>();
+    if (pl.ktable) {
+        K.kstart = pl.d_kstart.as<int64_t>();
+        K.kslot = pl.d_kslot.as<uint32_t>();
+        K.nsteps = (uint32_t)pl.kt_start.size();
+    } else if (pl.interval > 0 && pl.interval < (1ll << 32)) {
+        const MagicU32 mg = make_magic((uint32_t)pl.interval);
+        K.mg_m = mg.m; K.mg_s1 = mg.s1; K.mg_s2 = mg.s2;
+        K.keys32 = (uint32_t)(0xFFFFFFFFull / (uint64_t)pl.interval);
+    }
+    CollectParams Z{};
+    Z.n_docs = s->max_doc;
+    Z.n_blocks = n_blocks;
+    Z.zmin = hc->zmin.as<int64_t>();
+    Z.zmax = hc->zmax.as<int64_t>();
+    Z.interval = pl.interval;
+    Z.offset = pl.offset;
+    Z.key0 = pl.key0;
+    Z.kstart = K.kstart;
+    Z.kslot = K.kslot;
+    Z.nsteps = K.nsteps;
+    int64_t* zkey = (int64_t*)p->s_zkey.ensure(p->ctx, (size_t)std::max(n_blocks, 1u) * 16);
+    unsigned long long* ud = nullptr;
+    if (p->zu_n < kZuSlots && (n_blocks + 255) / 256 <= kZuMaxWG) {
+        ud = (unsigned long long*)p->s_zu.ensure(p->ctx, (size_t)kZuSlots * kZuMaxWG * 8) + (size_t)p->zu_n * kZuMaxWG;
+        p->zu_g[p->zu_n] = (n_blocks + 255) / 256;  // (every workgroup writes its word: no zeroing)
+    }
+    launch_zone_keys(Z, zkey, p->stream, ud);
+    HIPX(hipGetLastError());
+    if (ud) {
+        p->zu_w[p->zu_n] = 8;
+        p->zu_nw[p->zu_n] = 0;
+        ++p->zu_n;
+    }
+    K.zkey = zkey;
+    *bytes += 8ull * s->max_doc + 16ull * n_blocks;
+}
+
+// The grid for this segment -- R cells (allocated at a request's first segment; the value counts split from the doc
+// counts when the metric field turns sparse), or the [H][R] cells of a path-13 pipeline (mask_hist_shape; hc its
+// timestamp column) -- the metric column, the doc range, the grid pointers and the compensated sums into P; the metric
+// column's bytes into *bytes.  Returns the kernel's MET.
 template <class PARAMS>
-static int mask_collect_begin(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, const DevColumn* mc, uint32_t R, uint32_t n_blocks,
-                              PARAMS& P, uint64_t* bytes) {
+static int mask_collect_begin(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, const DevColumn* mc, const DevColumn* hc, uint32_t R,
+                              uint32_t n_blocks, PARAMS& P, uint64_t* bytes) {
     // (an unmapped metric field collects nothing: the doc counts alone, and the value counts split from them)
     const bool sparse_metric = pl.met > 0 && (!mc || mc->present.p);
     const bool first_segment = !pl.allocated || pl.fresh;
-    if (first_segment) {
+    if (pl.hist_spec >= 0) {
+        mask_hist_shape(p, pl, hc, R, sparse_metric);
+    } else if (first_segment) {
         const int vcnt = sparse_metric ? 1 : 0;
         const bool same = pl.allocated && pl.T == R && pl.H == 1 && vcnt == pl.vcnt_mode;
         pl.T = R;
@@ -3238,9 +3404,10 @@ static int mask_collect_begin(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
         }
     }
     if (pl.dd && met > 0) {
+        const size_t cells = (size_t)R * pl.H;
         auto lo = [&](DevBuf& b) {
-            if (b.p && b.bytes >= (size_t)R * 8) return b.as<double>();
-            b.alloc(p->ctx, (size_t)R * 8 + (size_t)R * 2);
+            if (b.p && b.bytes >= cells * 8) return b.as<double>();
+            b.alloc(p->ctx, cells * 8 + cells * 2);
             HIPX(hipMemsetAsync(b.p, 0, b.bytes, p->stream));
             return b.as<double>();
         };
@@ -3254,7 +3421,7 @@ static int mask_collect_begin(esgpu_plan* p, Pipeline& pl, const esgpu_segment* 
 // then the launch over `cus x occupancy` workgroups and the folds of the compensated sums, between the pipeline's two
 // events.  occupancy() is asked when the launch configuration `okey` changes; launch(grid) starts the kernel.
 template <class PARAMS, class OCC, class LAUNCH>
-static void mask_collect_launch(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, const uint64_t* d_accept, PARAMS& P, uint32_t R,
+static void mask_collect_launch(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, const uint64_t* d_accept, PARAMS& P, size_t cells,
                                 uint64_t okey, OCC occupancy, LAUNCH launch, uint64_t bytes, int path) {
     PredDev pred[kMaxPreds];
     int32_t npred = 0;
@@ -3279,8 +3446,8 @@ static void mask_collect_launch(esgpu_plan* p, Pipeline& pl, const esgpu_segment
     P.blocks_per_wg = (P.n_blocks + slots - 1) / slots;
     launch((P.n_blocks + P.blocks_per_wg - 1) / P.blocks_per_wg);
     HIPX(hipGetLastError());
-    if (P.g_sum_lo) launch_dd_fold(P.g_sum, P.g_sum_lo, R, p->stream);
-    if (P.g_sq_lo) launch_dd_fold(P.g_sq, P.g_sq_lo, R, p->stream);
+    if (P.g_sum_lo) launch_dd_fold(P.g_sum, P.g_sum_lo, cells, p->stream);
+    if (P.g_sq_lo) launch_dd_fold(P.g_sq, P.g_sq_lo, cells, p->stream);
     HIPX(hipGetLastError());
     HIPX(hipEventRecord(pl.e1, p->stream));
     p->last_bytes += bytes;
@@ -3297,13 +3464,17 @@ static bool collect_range(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, c
     require(rc->type == ESGPU_COL_I64 || rc->type == ESGPU_COL_F64, ESGPU_ERR_UNSUPPORTED,
             "range over a keyword or murmur3 field runs on the CPU path");
     const DevColumn* mc = mask_metric_column(pl, s, "a range");
+    const bool keyed = pl.hist_spec >= 0;  // a date_histogram child: collect path 13
+    const DevColumn* hc = keyed ? mask_hist_column(pl, s) : nullptr;
+    require(!keyed || !rc->multi, ESGPU_ERR_UNSUPPORTED,
+            "a date_histogram under a range aggregation over a multi-valued field runs on the CPU path");
     const uint32_t n_blocks = s->n_pad / kBlockDocs;
     if (n_blocks == 0) return false;
     const uint32_t R = (uint32_t)rn.rbuckets.size();
     RangeParams P{};
     // algorithmic bytes: each column at the width read, CSR offsets, the clause columns, the doc bitset
     uint64_t bytes = rc->multi ? 8ull * rc->n_values + 8ull * s->max_doc : 8ull * s->max_doc;
-    const int met = mask_collect_begin(p, pl, s, mc, R, n_blocks, P, &bytes);
+    const int met = mask_collect_begin(p, pl, s, mc, hc, R, n_blocks, P, &bytes);
     const int kind = rc->type == ESGPU_COL_F64 ? 2 : 1;
     {
         std::vector<uint64_t> table;
@@ -3321,6 +3492,14 @@ static bool collect_range(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s, c
     P.rv_present = rc->multi ? nullptr : rc->present.as<uint64_t>();
     P.rv_off = rc->multi ? rc->offsets.as<uint64_t>() : nullptr;
     P.rv_f64 = kind == 2;
+    if (keyed) {
+        HistKeys K;
+        mask_hist_keys(p, pl, s, hc, n_blocks, K, &bytes);
+        mask_collect_launch(
+            p, pl, s, d_accept, P, (size_t)R * pl.H, 0x200u | (uint64_t)met, [&] { return mask_hist_occupancy(met, false); },
+            [&](uint32_t grid) { launch_mask_hist(P, K, met, grid, p->stream); }, bytes, 13);
+        return true;
+    }
     mask_collect_launch(
         p, pl, s, d_accept, P, R, ((uint64_t)met << 1) | (rc->multi ? 1u : 0u), [&] { return range_occupancy(met, rc->multi); },
         [&](uint32_t grid) { launch_range(P, met, grid, p->stream); }, bytes, 11);
@@ -3365,6 +3544,8 @@ static bool collect_filters(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s,
         ccols[c].clauses.push_back({f.slot, iv});
     }
     const DevColumn* mc = mask_metric_column(pl, s, "a filters aggregation");
+    const bool keyed = pl.hist_spec >= 0;  // a date_histogram child: collect path 13
+    const DevColumn* hc = keyed ? mask_hist_column(pl, s) : nullptr;
     FiltersParams P{};
     std::vector<uint64_t> table(std::max<size_t>(ccols.size(), 1) * kFilterStride, 0);
     uint64_t bytes = 0;
@@ -3379,7 +3560,7 @@ static bool collect_filters(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s,
     }
     const uint32_t n_blocks = s->n_pad / kBlockDocs;
     if (n_blocks == 0) return false;
-    const int met = mask_collect_begin(p, pl, s, mc, R, n_blocks, P, &bytes);
+    const int met = mask_collect_begin(p, pl, s, mc, hc, R, n_blocks, P, &bytes);
     if (table != pl.ftable) {  // (the same request over the same dictionaries: the tables are on the device already)
         if (pl.d_ftable.bytes < (size_t)kFilterCols * kFilterStride * 8) pl.d_ftable.alloc(p->ctx, (size_t)kFilterCols * kFilterStride * 8);
         pl.ftable = std::move(table);  // the copy's source lives with the pipeline: the collect stays asynchronous
@@ -3396,6 +3577,14 @@ static bool collect_filters(esgpu_plan* p, Pipeline& pl, const esgpu_segment* s,
     P.R = R;
     P.other_bit = fn.other_bucket ? fn.n_filters : -1;
     P.all_mask = fn.n_filters >= 64 ? ~0ull : (1ull << fn.n_filters) - 1ull;
+    if (keyed) {
+        HistKeys K;
+        mask_hist_keys(p, pl, s, hc, n_blocks, K, &bytes);
+        mask_collect_launch(
+            p, pl, s, d_accept, P, (size_t)R * pl.H, 0x300u | (uint64_t)met, [&] { return mask_hist_occupancy(met, true); },
+            [&](uint32_t grid) { launch_mask_hist(P, K, met, grid, p->stream); }, bytes, 13);
+        return true;
+    }
     mask_collect_launch(
         p, pl, s, d_accept, P, R, 0x100u | (uint64_t)met, [&] { return filters_occupancy(met); },
         [&](uint32_t grid) { launch_filters(P, met, grid, p->stream); }, bytes, 12);
@@ -6781,8 +6970,63 @@ static Block build_hist_root(esgpu_plan* p, const Group& g) {
 
 static Block build_cardinality(esgpu_plan* p, Pipeline& pl);
 
+// ---- the buckets of a range / filters root: doc counts and children -------------------------------------------------
+// The group's grids on the host, and the R buckets' doc counts: pipes[0]'s cells, or -- pipes[0] carrying a
+// date_histogram child (path 13) -- the counts it keeps beside its [H][R] cells.
+static std::vector<int64_t> mask_root_counts(esgpu_plan* p, const Group& g, size_t R) {
+    for (int pi : g.pipes) {
+        Pipeline& pl = p->pipes[pi];
+        if (pl.allocated) fetch_grid(p, pl);
+    }
+    Pipeline& P0 = p->pipes[g.pipes[0]];
+    const bool keyed = P0.hist_spec >= 0;
+    if (P0.allocated && keyed) d2h_u64(p, P0.h_ocnt, P0.g_ocnt.p, R);
+    bsync(p);
+    std::vector<int64_t> counts(R, 0);
+    if (P0.allocated)
+        for (size_t k = 0; k < R; ++k) counts[k] = (int64_t)(keyed ? P0.h_ocnt.as<unsigned long long>()[k] : P0.hc.cnt[k]);
+    return counts;
+}
+
+// The children of bucket k, appended to r.subs: a metric from its pipeline's cell k; a date_histogram (path 13) as one
+// histogram instance from column k of its pipelines' [H][R] grids -- the rows with a doc count, keys ascending
+// (HistogramAggregator.buildAggregation), each with its leaves; a bucket no doc with a timestamp fell into carries the
+// empty histogram (buildEmptyAggregation), as does every bucket of a plan built without a collect.
+static void mask_root_children(esgpu_plan* p, const Group& g, size_t k, size_t R, Block& r) {
+    for (size_t ki = 0; ki < g.kids.size(); ++ki) {
+        const ChildSrc& kid = g.kids[ki];
+        Block& sub = r.subs[ki];
+        if (!kid.bucket) {
+            const Pipeline& L = p->pipes[kid.leaf.pipe];
+            if (L.allocated) append_leaf(p, L, kid.leaf.leaf, k, sub);
+            else sub.append_empty();
+            continue;
+        }
+        const Pipeline& B0 = p->pipes[kid.pipes[0]];
+        if (!B0.allocated || !B0.keyed) { sub.append_empty(); continue; }
+        std::vector<uint32_t> slots, cells;
+        std::vector<int64_t> counts;
+        for (uint32_t h = 0; h < B0.H; ++h) {
+            const unsigned long long c = B0.hc.cnt[(size_t)h * R + k];
+            if (c == 0) continue;
+            slots.push_back(h);
+            cells.push_back((uint32_t)((size_t)h * R + k));
+            counts.push_back((int64_t)c);
+        }
+        begin_instance(sub, 0);
+        append_hist_buckets(B0, slots, counts, sub);
+        for (size_t gj = 0; gj < kid.grand.size(); ++gj) {
+            const Pipeline& L = p->pipes[kid.grand[gj].pipe];
+            require(L.allocated && L.T == B0.T && L.H == B0.H && L.key0 == B0.key0, ESGPU_ERR_DEVICE,
+                    "sibling pipelines disagree on the key grid");
+            append_leaves(p, L, kid.grand[gj].leaf, cells, sub.subs[gj]);
+        }
+        end_instance(sub);
+    }
+}
+
 // RangeAggregator.buildAggregation (:198-209) / buildEmptyAggregation (:212-223): every range a bucket, in bucket order,
-// with its doc count (pipes[0]'s cells) and its leaves from their pipelines' cells -- cell == bucket position
+// with its doc count and its children (mask_root_counts / mask_root_children)
 static Block build_range_root(esgpu_plan* p, const Group& g) {
     const SpecNode& n = p->specs[g.root];
     Block r;
@@ -6793,31 +7037,22 @@ static Block build_range_root(esgpu_plan* p, const Group& g) {
     r.boff.assign(1, 0);
     r.term_off.assign(1, 0);
     for (const Block& b : child_protos(p, g)) r.subs.push_back(b.like());
-    for (int pi : g.pipes) {
-        Pipeline& pl = p->pipes[pi];
-        if (pl.allocated) fetch_grid(p, pl);
-    }
-    bsync(p);
-    const Pipeline& P0 = p->pipes[g.pipes[0]];
+    const size_t R = n.rbuckets.size();
+    const std::vector<int64_t> counts = mask_root_counts(p, g, R);
     begin_instance(r, 0);
-    for (size_t k = 0; k < n.rbuckets.size(); ++k) {
+    for (size_t k = 0; k < R; ++k) {
         const RangeBucket& rb = n.rbuckets[k];
-        push_bucket(r, (int64_t)k, &rb.key, P0.allocated ? (int64_t)P0.hc.cnt[k] : 0);
+        push_bucket(r, (int64_t)k, &rb.key, counts[k]);
         r.rfrom.push_back(rb.from);
         r.rto.push_back(rb.to);
-        for (size_t ki = 0; ki < g.kids.size(); ++ki) {
-            const Pipeline& L = p->pipes[g.kids[ki].leaf.pipe];
-            if (L.allocated) append_leaf(p, L, g.kids[ki].leaf.leaf, k, r.subs[ki]);
-            else r.subs[ki].append_empty();
-        }
+        mask_root_children(p, g, k, R, r);
     }
     end_instance(r);
     return r;
 }
 
 // FiltersAggregator.buildAggregation (:113-129) / buildEmptyAggregation (:132-146): every filter a bucket, in request
-// order, then the other bucket, with its doc count (pipes[0]'s cells) and its leaves from their pipelines' cells -- cell
-// == bucket position
+// order, then the other bucket, with its doc count and its children (mask_root_counts / mask_root_children)
 static Block build_filters_root(esgpu_plan* p, const Group& g) {
     const SpecNode& n = p->specs[g.root];
     Block r;
@@ -6827,20 +7062,12 @@ static Block build_filters_root(esgpu_plan* p, const Group& g) {
     r.boff.assign(1, 0);
     r.term_off.assign(1, 0);
     for (const Block& b : child_protos(p, g)) r.subs.push_back(b.like());
-    for (int pi : g.pipes) {
-        Pipeline& pl = p->pipes[pi];
-        if (pl.allocated) fetch_grid(p, pl);
-    }
-    bsync(p);
-    const Pipeline& P0 = p->pipes[g.pipes[0]];
+    const size_t R = n.fkeys.size();
+    const std::vector<int64_t> counts = mask_root_counts(p, g, R);
     begin_instance(r, 0);
-    for (size_t k = 0; k < n.fkeys.size(); ++k) {
-        push_bucket(r, (int64_t)k, &n.fkeys[k], P0.allocated ? (int64_t)P0.hc.cnt[k] : 0);
-        for (size_t ki = 0; ki < g.kids.size(); ++ki) {
-            const Pipeline& L = p->pipes[g.kids[ki].leaf.pipe];
-            if (L.allocated) append_leaf(p, L, g.kids[ki].leaf.leaf, k, r.subs[ki]);
-            else r.subs[ki].append_empty();
-        }
+    for (size_t k = 0; k < R; ++k) {
+        push_bucket(r, (int64_t)k, &n.fkeys[k], counts[k]);
+        mask_root_children(p, g, k, R, r);
     }
     end_instance(r);
     return r;

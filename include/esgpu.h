@@ -255,12 +255,18 @@ enum {
      * (double) v < to; a doc without a value is in no range; overlapping, identical, from == to and from > to ranges are
      * legal.  Every range is a bucket, empty or not, in the order of esgpu_range_buckets (sorted by from, then to).
      * Sub-aggregations: stats, extended_stats, avg, sum, min, max, value_count over single-valued long / double
-     * fields.  Result block: n_buckets = the ranges per instance, doc_counts, subs, the keys in term_offsets / term_bytes,
-     * the bounds in range_from / range_to, keyed, value_format / format / time_zone.
+     * fields, and date_histograms (ESGPU_AGG_DATE_HISTOGRAM, every parameter of a top-level one) over a single-valued long
+     * field with such metrics below them: sub-block j then holds one histogram instance per range, the empty histogram
+     * for a range no doc with a timestamp fell into.  A doc of a range without a timestamp counts in the range and in no
+     * histogram bucket.  Result block: n_buckets = the ranges per instance, doc_counts, subs, the keys in term_offsets /
+     * term_bytes, the bounds in range_from / range_to, keyed, value_format / format / time_zone.
      * Refused with ESGPU_ERR_INVALID: no ranges, a NaN bound.  Refused with ESGPU_ERR_UNSUPPORTED (the plugin keeps the
      * Java aggregator): more than 64 ranges (a doc's ranges are one u64 mask); a range that is not top level (under a
-     * filter aggregation included); a bucket, filter or cardinality sub-aggregation; a keyword or ESGPU_COL_U64 range
-     * field; a multi-valued metric field, or value_count over a keyword or multi-valued field, under a range;
+     * filter aggregation included); a bucket other than a date_histogram (the numeric histogram included: the decision is
+     * by spec type), a filter or a cardinality sub-aggregation, and any of them below that date_histogram; a keyword or
+     * ESGPU_COL_U64 range field; a multi-valued metric field, or value_count over a keyword or multi-valued field, under
+     * a range; with a date_histogram child, at the first collect that shows it: a multi-valued range field, a
+     * date_histogram field that is not a single-valued ESGPU_COL_I64 column, a grid of keys x ranges over 2^31 cells;
      * ESGPU_FORMAT_NUMBER on the range (its keys would need DecimalFormat); a date format other than the mapping's
      * default (strict_date_optional_time, with or without ||epoch_millis), which is all the date printer prints.
      * date_range, ip_range, geo_distance and string bounds (date math) are not covered. */
@@ -270,15 +276,19 @@ enum {
      * of the esgpu_filter clauses with owner = this spec + 1 and slot = i; a filter without a clause is match_all.  A doc
      * is in every bucket whose filter it matches.  Clauses: ESGPU_FILTER_TERM / ESGPU_FILTER_RANGE over single-valued
      * keyword, long / date and double columns, dense or sparse (a doc without a value matches no clause on the column).
-     * Sub-aggregations: stats, extended_stats, avg, sum, min, max, value_count over single-valued long / double fields.
+     * Sub-aggregations: stats, extended_stats, avg, sum, min, max, value_count over single-valued long / double fields,
+     * and date_histograms with such metrics below them, as under ESGPU_AGG_RANGE above (one histogram instance per
+     * bucket, the other bucket included).
      * Result block: n_buckets = the buckets per instance, doc_counts, subs, the keys in term_offsets / term_bytes, keyed.
-     * A plan built without a collect has every bucket, the other one included, with count 0.
+     * A plan built without a collect has every bucket, the other one included, with count 0 (and the empty histogram).
      * Refused with ESGPU_ERR_INVALID: no filter.  Refused with ESGPU_ERR_UNSUPPORTED at esgpu_plan_create (the plugin
      * keeps the Java aggregator): more than 64 buckets, the other bucket included (a doc's buckets are one u64 mask); a
-     * filters aggregation that is not top level; a bucket, filter or cardinality sub-aggregation.  Refused with
+     * filters aggregation that is not top level; a bucket other than a date_histogram (the numeric histogram included), a
+     * filter or a cardinality sub-aggregation, and any of them below that date_histogram.  Refused with
      * ESGPU_ERR_UNSUPPORTED at the first collect that shows it: more than 4 distinct clause columns; more than 128
      * distinct cuts (clause bounds) on one column; a multi-valued or ESGPU_COL_U64 clause column; a clause field missing
-     * from the segment; a non-numeric or multi-valued metric field. */
+     * from the segment; a non-numeric or multi-valued metric field; a date_histogram field that is not a single-valued
+     * ESGPU_COL_I64 column; a grid of keys x buckets over 2^31 cells. */
     ESGPU_AGG_FILTERS = 14
 };
 
@@ -489,7 +499,10 @@ int esgpu_plan_destroy(esgpu_plan* plan);
  * bytes read, CSR offsets, the doc bitset of a filtered request and the columns its clauses read), 12 the filters collect
  * (one pass over the distinct clause columns and one metric field per pipeline; bytes: each distinct clause column once
  * at the width read -- 4 for ordinals, 8 otherwise --, the metric column at 8, the doc bitset of a filtered request and
- * the columns that bitset's clauses read). */
+ * the columns that bitset's clauses read), 13 the keyed form of 11 / 12 for a date_histogram child (one pass per metric
+ * field of the histogram's children; bytes: what 11 / 12 count, plus 8 per timestamp for every doc of a zone block of
+ * 8,192 docs that is not single-key -- the timestamps of single-key blocks are not read -- plus 16 per zone block for
+ * its key range). */
 int esgpu_plan_last_collect_stats(const esgpu_plan* plan, double* kernel_ms, uint64_t* algorithmic_bytes,
                                   int32_t* path);
 /* The kernel that ran the last collect's LDS-window launch: 0 the generic collect kernel, 1 the ranked kernel (path 10

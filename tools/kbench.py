@@ -30,11 +30,16 @@ def variants():
         AB.dateHistogram("h").field("@timestamp").interval("1h").subAggregation(m))
     # five latency classes over response_time_ms, each with stats(bytes): as one range aggregation (one pass over the two
     # columns), as its twin, five top-level filter aggregations with a gte / lt range clause and the same child, and as
-    # one filters aggregation of the same five clauses (one pass over the two columns)
+    # one filters aggregation of the same five clauses (one pass over the two columns); and the same three with an hourly
+    # date_histogram between the classes and the stats (*_dh_stats: the keyed one-pass forms against five passes)
     cuts = [None, 50, 100, 250, 500, None]
+    dh_b = lambda: AB.dateHistogram("h").field("@timestamp").interval("1h").subAggregation(AB.stats("b").field("bytes"))  # noqa: E731
     rng = AB.range("lat").field("response_time_ms").subAggregation(AB.stats("b").field("bytes"))
     flt5 = []
     fagg = AB.filters("lat").subAggregation(AB.stats("b").field("bytes"))
+    rng_dh = AB.range("lat").field("response_time_ms").subAggregation(dh_b())
+    flt5_dh = []
+    fagg_dh = AB.filters("lat").subAggregation(dh_b())
     for k, (lo, hi) in enumerate(zip(cuts[:-1], cuts[1:])):
         rng.addRange(float("-inf") if lo is None else lo, float("inf") if hi is None else hi)
         q = QB.rangeQuery("response_time_ms")
@@ -42,10 +47,16 @@ def variants():
         q = q if hi is None else q.lt(hi)
         flt5.append(AB.filter("f%d" % k, q).subAggregation(AB.stats("b").field("bytes")))
         fagg.filter("f%d" % k, q)
+        rng_dh.addRange(float("-inf") if lo is None else lo, float("inf") if hi is None else hi)
+        flt5_dh.append(AB.filter("f%d" % k, q).subAggregation(dh_b()))
+        fagg_dh.filter("f%d" % k, q)
     return {
         "range5_stats": ([rng], None),
         "filters5_stats": (flt5, None),
         "filters_agg5_stats": ([fagg], None),
+        "range5_dh_stats": ([rng_dh], None),
+        "filters5_dh_stats": (flt5_dh, None),
+        "filters_agg5_dh_stats": ([fagg_dh], None),
         "terms_host": ([AB.terms("hosts").field("host")], None),
         "date_hist": ([AB.dateHistogram("h").field("@timestamp").interval("1h")], None),
         "config2_dh_ext": ([AB.dateHistogram("h").field("@timestamp").interval("1h").subAggregation(
