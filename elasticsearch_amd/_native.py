@@ -31,7 +31,8 @@ ORDER_KEY_ASC, ORDER_KEY_DESC, ORDER_HCOUNT_ASC, ORDER_HCOUNT_DESC = 4, 5, 6, 7
 ORDER_AGG_ASC, ORDER_AGG_DESC = 8, 9
 FORMAT_RAW, FORMAT_DATE_TIME, FORMAT_NUMBER = 0, 1, 2
 UNIT_NONE, UNIT_WEEK, UNIT_YEAR, UNIT_QUARTER, UNIT_MONTH, UNIT_DAY, UNIT_HOUR, UNIT_MINUTE, UNIT_SECOND = range(9)
-FILTER_TERM, FILTER_RANGE = 1, 2
+FILTER_TERM, FILTER_RANGE, FILTER_TERMS, FILTER_EXISTS, FILTER_BOOL = 1, 2, 3, 4, 5
+OCCUR_MUST, OCCUR_SHOULD, OCCUR_MUST_NOT = 0, 1, 2
 COMM_ID_BYTES = 128
 DT_U8, DT_I64, DT_U64, DT_F64 = 0, 1, 2, 3
 RED_SUM, RED_MIN, RED_MAX = 0, 1, 2
@@ -78,6 +79,9 @@ class Filter(ctypes.Structure):
         ("lo_term", ctypes.c_char_p), ("hi_term", ctypes.c_char_p), ("lo_term_len", ctypes.c_uint64),
         ("hi_term_len", ctypes.c_uint64),
         ("slot", ctypes.c_int32), ("reserved_slot", ctypes.c_int32),  # the filter of a filters aggregation (owner)
+        # bool form (include/esgpu.h "Query filters"): OCCUR_*, the clause group, the values of a TERMS clause
+        ("occur", ctypes.c_int32), ("group", ctypes.c_int32),
+        ("terms", ctypes.POINTER(ctypes.c_int64)), ("n_terms", ctypes.c_uint64),
     ]
 
 
@@ -176,6 +180,7 @@ SIGNATURES = [
     ("esgpu_plan_last_collect_stats", ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64),
                                                      ctypes.POINTER(ctypes.c_int32)]),
     ("esgpu_plan_last_collect_kernel", ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_int32)]),
+    ("esgpu_plan_last_doc_bitset_stats", ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]),
     ("esgpu_plan_last_collect_read_bytes", ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_uint64)]),
     ("esgpu_plan_last_build_stats", ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     ("esgpu_plan_shard_mergeable", ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_int32)]),

@@ -14,6 +14,7 @@ import ctypes
 import functools
 import math
 import re
+import struct
 
 from . import _native as N
 
@@ -323,7 +324,8 @@ class CardinalityBuilder(_MetricBuilder):
 
 class FilterBuilder(_Builder):
     """filter aggregation (FilterAggregator / InternalFilter): one bucket of the docs matching `query` -- a TermQuery,
-    a RangeQuery or a list of them (bool.filter conjunction) -- with sub-aggregations.  On the GPU path at the top level
+    a RangeQuery or a list of them (bool.filter conjunction), or, at the top level, any leaf or BoolQuery -- with
+    sub-aggregations.  On the GPU path at the top level
     (any sub-aggregations) or directly under a top-level bucket aggregation (metric sub-aggregations)."""
     type = N.AGG_FILTER
 
@@ -456,7 +458,7 @@ class AggregationBuilders:
     cardinality = CardinalityBuilder
 
 
-# ---- queries (bool.filter conjunction of term / range) ----
+# ---- queries: term / range / terms / exists leaves and bool (a list is a conjunction: bool.filter) ----
 class TermQuery:
     def __init__(self, field, value):
         self.field, self.value = field, value
@@ -493,6 +495,89 @@ class RangeQuery:
         return self
 
 
+class TermsQuery:
+    """terms (TermsQueryBuilder): the doc's value is one of `values`; an empty list matches no doc"""
+
+    def __init__(self, field, values):
+        self.field, self.values = field, list(values)
+
+
+class ExistsQuery:
+    """exists (ExistsQueryBuilder): the doc has a value in the field"""
+
+    def __init__(self, field):
+        self.field = field
+
+
+class BoolQuery:
+    """bool (BoolQueryBuilder): must and filter clauses are required alike (nothing is scored), must_not clauses
+    prohibited, should clauses optional; minimum_should_match as Queries.calculateMinShouldMatch reads it (an int or a
+    string: "2", "-1", "75%", "-25%", "3<90%", "2<-25% 9<-3")."""
+
+    def __init__(self):
+        self.must_clauses, self.filter_clauses, self.should_clauses, self.must_not_clauses = [], [], [], []
+        self._msm = None       # the minimum_should_match spec as given, or None
+        self._adjust = True    # adjust_pure_negative
+
+    def must(self, q):
+        self.must_clauses.append(q)
+        return self
+
+    def filter(self, q):
+        self.filter_clauses.append(q)
+        return self
+
+    def should(self, q):
+        self.should_clauses.append(q)
+        return self
+
+    def mustNot(self, q):  # noqa: N802
+        self.must_not_clauses.append(q)
+        return self
+
+    def minimumShouldMatch(self, spec):  # noqa: N802
+        self._msm = None if spec is None else str(spec)
+        return self
+
+    def adjustPureNegative(self, adjust):  # noqa: N802
+        self._adjust = bool(adjust)
+        return self
+
+    must_not = mustNot
+    minimum_should_match = minimumShouldMatch
+    adjust_pure_negative = adjustPureNegative
+
+
+def _f32(x):
+    return struct.unpack("<f", struct.pack("<f", x))[0]
+
+
+def calculate_min_should_match(optional_clause_count, spec):
+    """Queries.calculateMinShouldMatch (common/lucene/search/Queries.java:142-177), its float32 arithmetic and its
+    truncation toward zero included.  A malformed spec raises ValueError, as Integer.parseInt throws."""
+    result = n = int(optional_clause_count)
+    spec = str(spec).strip()
+    if "<" in spec:  # conditional spec(s)
+        spec = re.sub(r"(\s+<\s*)|(\s*<\s+)", "<", spec)
+        for s in spec.split(" "):
+            parts = [x for x in s.split("<")]
+            while parts and parts[-1] == "":  # String.split(regex, 0) drops trailing empty strings
+                parts.pop()
+            upper = int(parts[0])
+            if n <= upper:
+                return result
+            result = calculate_min_should_match(n, parts[1])
+        return result
+    if "%" in spec:
+        percent = int(spec[:-1])
+        calc = _f32(_f32(float(result * percent)) * _f32(1 / _f32(100.0)))
+        result = result + int(calc) if calc < 0 else int(calc)  # (int) of a float truncates toward zero, as int() does
+    else:
+        calc = int(spec)
+        result = result + calc if calc < 0 else calc
+    return n if n < result else (0 if result < 0 else result)
+
+
 class QueryBuilders:
     @staticmethod
     def termQuery(field, value):  # noqa: N802
@@ -502,8 +587,28 @@ class QueryBuilders:
     def rangeQuery(field):  # noqa: N802
         return RangeQuery(field)
 
+    @staticmethod
+    def termsQuery(field, values):  # noqa: N802
+        return TermsQuery(field, values)
+
+    @staticmethod
+    def existsQuery(field):  # noqa: N802
+        return ExistsQuery(field)
+
+    @staticmethod
+    def missingQuery(field):  # noqa: N802 -- MissingQueryBuilder's defaults (existence true, null_value false)
+        return BoolQuery().mustNot(ExistsQuery(field))
+
+    @staticmethod
+    def boolQuery():  # noqa: N802
+        return BoolQuery()
+
     term_query = termQuery
     range_query = rangeQuery
+    terms_query = termsQuery
+    exists_query = existsQuery
+    missing_query = missingQuery
+    bool_query = boolQuery
 
 
 # ---- flattening -------------------------------------------------------------------------------------------------
@@ -680,25 +785,132 @@ def _bound_i64(v):
     return int(v)
 
 
+_LEAVES = (TermQuery, RangeQuery, TermsQuery, ExistsQuery)
+
+
+def _nesting(what):
+    return N.UnsupportedOnGpu(N.ERR_UNSUPPORTED, "%s: this bool nesting runs on the CPU path" % what)
+
+
+def _is_should_group(q):
+    """a nested bool of only should leaves whose minimum_should_match is unset or asks for one: it holds when any of its
+    leaves holds"""
+    if not isinstance(q, BoolQuery) or q.must_clauses or q.filter_clauses or q.must_not_clauses or not q.should_clauses:
+        return False
+    if not all(isinstance(c, _LEAVES) for c in q.should_clauses):
+        return False
+    return q._msm is None or calculate_min_should_match(len(q.should_clauses), q._msm) in (0, 1)  # (0: the default, one)
+
+
+def lower_query(query, keep_empty=False):
+    """One owner's query -- a leaf, a list (a conjunction: bool.filter) or a BoolQuery -- in the normal form of
+    include/esgpu.h "Query filters": -> ([(leaf, occur, group)], options), options = (resolved minimum_should_match or
+    -1, adjust_pure_negative) for bool form and None for plain form (only required term / range leaves; an owner
+    without a clause is plain unless keep_empty: a filter aggregation's match_all needs its options record).
+    A clause that is itself a bool becomes a group in its position when it is a bool of only should leaves
+    (minimum_should_match unset or 1), and is flattened when it is a bool of only must / filter clauses in a must /
+    filter position; any other nesting raises UnsupportedOnGpu."""
+    while isinstance(query, (list, tuple)) and len(query) == 1:
+        query = query[0]  # (a conjunction of one clause is that clause)
+    if isinstance(query, (list, tuple)):
+        top = BoolQuery()
+        top.filter_clauses = list(query)
+    elif isinstance(query, BoolQuery):
+        top = query
+    else:
+        top = BoolQuery().filter(query)
+    clauses, groups = [], [0]
+
+    def group_of(q, occur):
+        groups[0] += 1
+        clauses.extend((leaf, occur, groups[0]) for leaf in q.should_clauses)
+
+    def required(q):
+        if isinstance(q, _LEAVES):
+            clauses.append((q, N.OCCUR_MUST, 0))
+        elif isinstance(q, (list, tuple)) and len(q) > 0:
+            for c in q:
+                required(c)
+        elif _is_should_group(q):
+            group_of(q, N.OCCUR_MUST)
+        elif (isinstance(q, BoolQuery) and (q.must_clauses or q.filter_clauses) and not q.should_clauses
+              and not q.must_not_clauses):
+            for c in q.must_clauses + q.filter_clauses:
+                required(c)
+        else:
+            raise _nesting("a must / filter clause that is neither a leaf, a conjunction nor a bool of should leaves")
+
+    for c in top.must_clauses + top.filter_clauses:
+        required(c)
+    for occur, cs, name in ((N.OCCUR_SHOULD, top.should_clauses, "should"), (N.OCCUR_MUST_NOT, top.must_not_clauses, "must_not")):
+        for c in cs:
+            if isinstance(c, _LEAVES):
+                clauses.append((c, occur, 0))
+            elif _is_should_group(c):
+                group_of(c, occur)
+            else:
+                raise _nesting("a %s clause that is neither a leaf nor a bool of should leaves" % name)
+    plain = all(isinstance(q, (TermQuery, RangeQuery)) and occur == N.OCCUR_MUST and group == 0 for q, occur, group in clauses)
+    if plain and (clauses or not keep_empty):
+        return clauses, None
+    msm = -1 if top._msm is None else calculate_min_should_match(len(top.should_clauses), top._msm)
+    return clauses, (msm, top._adjust)
+
+
 def flatten_filters(queries, ord_lookup=None, aggs=None):
     """Queries -> ctypes array of Filter.  `ord_lookup(field, term) -> ordinal or -1` resolves keyword terms.  With
     `aggs`, the clauses of every filter aggregation follow, each tagged with its owner (spec index + 1), and those of
     every filters aggregation, tagged with the owner and the slot of their filter."""
     out, keep = [], []
-    tagged = [(q, 0, 0) for q in queries or []]
+    tagged = []  # (leaf or None for an owner's options record, owner, slot, occur, group, (msm, adjust))
+
+    def add_owner(query, owner, slot, keep_empty=False):
+        clauses, options = lower_query(query, keep_empty)
+        tagged.extend((q, owner, slot, occur, group, None) for q, occur, group in clauses)
+        if options is not None:
+            tagged.append((None, owner, slot, 0, 0, options))
+
+    add_owner(BoolQuery() if queries is None else queries, 0, 0)
     for b, i in _preorder(aggs):
         if b.type == N.AGG_FILTER:
-            tagged += [(q, i + 1, 0) for q in b.clauses()]
+            q = b._query
+            if q is None:
+                raise ValueError("[filter] aggregation [%s] requires a filter" % b.name)
+            add_owner(q, i + 1, 0, keep_empty=isinstance(q, BoolQuery))  # (an empty bool is match_all)
         elif b.type == N.AGG_FILTERS:
-            tagged += [(q, i + 1, slot) for slot, (_key, qs) in enumerate(b.filters()[1]) for q in qs]
-    for q, owner, slot in tagged:
+            for slot, (_key, qs) in enumerate(b.filters()[1]):
+                add_owner(qs, i + 1, slot)
+
+    def term_value(field, v):
+        if isinstance(v, str):
+            if ord_lookup is None:
+                raise ValueError("keyword term filters need an ordinal lookup")
+            v = ord_lookup(field, v)
+        return int(v)
+
+    for q, owner, slot, occur, group, options in tagged:
         f = N.Filter()
         f.owner = owner
         f.slot = slot
+        f.occur = occur
+        f.group = group
+        if q is None:  # the owner's options: the resolved minimum_should_match (-1: not given), adjust_pure_negative
+            f.type = N.FILTER_BOOL
+            f.term, f.include_lower = options[0], int(options[1])
+            out.append(f)
+            continue
         b = q.field.encode("utf-8")
         keep.append(b)
         f.field = b
-        if isinstance(q, TermQuery):
+        if isinstance(q, ExistsQuery):
+            f.type = N.FILTER_EXISTS
+        elif isinstance(q, TermsQuery):
+            f.type = N.FILTER_TERMS
+            vals = (ctypes.c_int64 * max(len(q.values), 1))(*[term_value(q.field, v) for v in q.values])
+            keep.append(vals)
+            f.terms = ctypes.cast(vals, ctypes.POINTER(ctypes.c_int64))
+            f.n_terms = len(q.values)
+        elif isinstance(q, TermQuery):
             f.type = N.FILTER_TERM
             v = q.value
             if isinstance(v, str):

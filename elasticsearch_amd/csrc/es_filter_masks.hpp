@@ -18,6 +18,10 @@
 // (a filter without a clause there: everywhere; two clauses of one filter intersect, possibly to nothing).  One more
 // mask is for a doc without a value in the column -- a clear present bit, the missing ordinal, NaN: the filters without
 // a clause on the column.  A doc's filters are the AND of its masks over the clause columns.
+//
+// A bool query (ESGPU_FILTER_TERMS / EXISTS / BOOL, occur, group) uses the same tables with the leaf as the slot:
+// build_leaf_masks lets a leaf accept a union of intervals, BoolComb / bool_comb_match evaluate the owner's clauses on a
+// doc's leaf mask (csrc/check/bool_query_check.cpp runs them stand-alone; esgpu_bool_bits.hip on the device).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -149,6 +153,127 @@ inline bool build_filter_masks(const std::vector<FilterClause>& clauses, int32_t
     table[kFilterMaskNoValue] = all & ~with_clause;
     *n_cuts = n;
     return true;
+}
+
+// ---- the leaves of a bool query ---------------------------------------------------------------------------------------
+// A bool query's leaf (term, range, terms, exists) is the slot of the same tables: bit i of a doc's mask says that leaf i
+// holds for the doc.  A leaf has a clause only on its own column and is all ones on the others, so the AND over the
+// columns is the doc's leaf mask.  A terms leaf is a union of [t, t]; exists is the whole domain.
+struct LeafClause {
+    int32_t slot;                  // the leaf: bit `slot` of the masks
+    std::vector<KeyInterval> ivs;  // the keys it accepts: their union (none: an empty terms list, no key)
+    bool exists = false;           // an exists leaf: see nan_is_value below
+};
+
+// build_filter_masks with a union of intervals per leaf.  The no-value mask is for a doc without a value in the column:
+// the leaves without a clause on it.  nan_is_value (a double column, whose lookup hands a NaN the no-value mask too): the
+// exists leaves are set in it as well, and *exists_mask names them -- the caller clears them for a doc whose present bit
+// is clear.  false: more than kFilterMaskCuts distinct cuts.
+inline bool build_leaf_masks(const std::vector<LeafClause>& leaves, int32_t n_leaves, KeyInterval domain, bool nan_is_value,
+                             uint64_t* table, uint32_t* n_cuts, uint64_t* exists_mask) {
+    const uint64_t all = n_leaves >= 64 ? ~0ull : (1ull << n_leaves) - 1ull;
+    std::vector<int64_t> cuts;
+    std::vector<std::vector<KeyInterval>> clipped(leaves.size());
+    uint64_t with_clause = 0, ex = 0;
+    for (size_t i = 0; i < leaves.size(); ++i) {
+        with_clause |= 1ull << leaves[i].slot;
+        if (leaves[i].exists) ex |= 1ull << leaves[i].slot;
+        for (const KeyInterval& raw : leaves[i].ivs) {
+            KeyInterval iv = key_intersect(raw, domain);
+            if (iv.empty()) continue;
+            // the whole domain is the whole key line (no key outside it is looked up): no cut
+            if (iv.lo == domain.lo && iv.hi == domain.hi) iv = {INT64_MIN, INT64_MAX};
+            clipped[i].push_back(iv);
+            if (iv.lo > INT64_MIN) cuts.push_back(iv.lo);
+            if (iv.hi < INT64_MAX) cuts.push_back(iv.hi + 1);
+        }
+    }
+    std::sort(cuts.begin(), cuts.end());
+    cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+    if (cuts.size() > kFilterMaskCuts) return false;
+    std::fill(table, table + kFilterMaskStride, 0ull);
+    const uint32_t n = (uint32_t)cuts.size();
+    for (uint32_t k = 0; k < n; ++k) table[k] = (uint64_t)cuts[k];
+    for (uint32_t k = 0; k <= n; ++k) {
+        // every bound is a cut, so an elementary interval lies wholly inside or outside each leaf interval
+        const int64_t rep = k == 0 ? INT64_MIN : cuts[k - 1];
+        uint64_t m = all;
+        for (size_t i = 0; i < leaves.size(); ++i) {
+            bool holds = false;
+            for (const KeyInterval& iv : clipped[i]) holds = holds || iv.holds(rep);
+            if (!holds) m &= ~(1ull << leaves[i].slot);
+        }
+        table[kFilterMaskCuts + k] = m;
+    }
+    table[kFilterMaskNoValue] = (all & ~with_clause) | (nan_is_value ? ex : 0ull);
+    *n_cuts = n;
+    *exists_mask = nan_is_value ? ex : 0ull;
+    return true;
+}
+
+// The combinator of one owner's clauses over a doc's leaf mask (BoolQueryBuilder.doToQuery, Queries.applyMinimumShouldMatch
+// / fixNegativeQueryIfNeeded, BooleanQuery's matching rules).  A clause is one leaf or a group of leaves that holds when
+// any of them holds (a nested bool of should leaves).
+constexpr uint32_t kBoolLeaves = 64;
+constexpr uint32_t kBoolGroups = kBoolLeaves / 2;  // multi-leaf clauses at most
+struct BoolComb {
+    uint64_t must;                 // the single-leaf required clauses (must and filter alike)
+    uint64_t must_not;             // every prohibited leaf (a prohibited group is an OR: one mask covers all of them)
+    uint64_t should;               // the single-leaf optional clauses, counted by popcount
+    uint64_t group[kBoolGroups];   // multi-leaf clauses: the first n_must_groups required, the others optional
+    uint32_t n_must_groups, n_groups;
+    int32_t m;                     // optional clauses that must hold at least
+    int32_t match_none;            // only prohibited clauses and adjust_pure_negative false
+};
+
+#if defined(__HIPCC__)
+#define FM_HD __host__ __device__ inline
+#else
+#define FM_HD inline
+#endif
+FM_HD bool bool_comb_match(const BoolComb& c, uint64_t leaves) {
+    bool ok = !c.match_none && (leaves & c.must) == c.must && (leaves & c.must_not) == 0;
+    int32_t opt = __builtin_popcountll(leaves & c.should);
+    for (uint32_t g = 0; g < c.n_groups; ++g) {
+        const bool holds = (leaves & c.group[g]) != 0;
+        if (g < c.n_must_groups) ok = ok && holds;
+        else opt += holds ? 1 : 0;
+    }
+    return ok && opt >= c.m;
+}
+#undef FM_HD
+
+// one clause of an owner as the C-ABI states it: the leaves' bits (one bit: a leaf by itself; more: a group) and its occur
+struct BoolClauseBits {
+    uint64_t leaves;
+    int32_t occur;  // ESGPU_OCCUR_*
+};
+// m as BooleanQuery applies it: the resolved minimum_should_match when it is > 0 (msm < 0: not given), else 1 when there
+// is no required clause and an optional one, else 0.  No clause at all is match_all; only prohibited clauses match the
+// docs none of them holds for when adjust_pure_negative, else no doc.
+inline BoolComb make_bool_comb(const std::vector<BoolClauseBits>& clauses, int64_t msm, bool adjust_pure_negative) {
+    BoolComb c{};
+    uint32_t n_must = 0, n_should = 0, n_not = 0;
+    for (int pass = 0; pass < 2; ++pass)  // required groups first
+        for (const BoolClauseBits& cl : clauses) {
+            const bool multi = (cl.leaves & (cl.leaves - 1)) != 0;
+            if (cl.occur == ESGPU_OCCUR_MUST_NOT) {
+                if (pass == 0) { c.must_not |= cl.leaves; ++n_not; }
+                continue;
+            }
+            const bool must = cl.occur == ESGPU_OCCUR_MUST;
+            if (pass == 0) (must ? n_must : n_should) += 1;
+            if (!multi) {
+                if (pass == 0) (must ? c.must : c.should) |= cl.leaves;
+            } else if (must == (pass == 0)) {
+                c.group[c.n_groups++] = cl.leaves;
+                if (must) ++c.n_must_groups;
+            }
+        }
+    c.m = msm > 0 ? (int32_t)std::min<int64_t>(msm, INT32_MAX) : (n_must == 0 && n_should > 0 ? 1 : 0);
+    if (clauses.empty()) c.m = 0;  // match_all, whatever minimum_should_match says (doToQuery returns before applying it)
+    c.match_none = n_not > 0 && n_must == 0 && n_should == 0 && !adjust_pure_negative;
+    return c;
 }
 
 // the lookup the kernel makes (branch-free binary search): the mask of the interval with exactly k cuts <= key

@@ -42,6 +42,7 @@
 #include "es_term_rank.hpp"
 #include "es_filter_masks.hpp"
 #include "esgpu_kernels.hpp"
+#include "esgpu_bool_bits.hpp"
 #include "esgpu_results.hpp"
 #include "esgpu_internal.hpp"
 #include "java_double.hpp"
@@ -1295,12 +1296,36 @@ struct esgpu_plan {
     Scratch s_drows;                   // build: composite ordinals a three-level child reads (fetch_rows)
     bool sparse_dead = false;          // the current segment's accept bitset clears few docs (host sample, <= 10 %)
     Scratch s_xbits;                   // doc bitset of a pipeline with more than kMaxPreds clauses
-    uint32_t seg_seq = 0;              // segments collected since create / reset (cardinality insertion order)
+    // owners whose clauses are in bool form (include/esgpu.h "Query filters"): the doc set of each is one bitset per
+    // segment, computed once per collect call (bool_bits_collect) and handed to the owner's pipelines as their accept
+    // bits; their clauses make no PredDev (applies)
+    struct BoolOwner {
+        int owner = -1;                    // -1 = the request query; r = the top-level filter aggregation spec r
+        std::vector<int> leaves;           // bit i of a doc's leaf mask: the clause filters[leaves[i]]
+        std::vector<BoolClauseBits> clauses;
+        BoolComb comb{};
+        DevBuf bits, table;                // the bitset (n_pad / 64 words of the current segment), the leaf columns' tables
+        std::vector<uint64_t> h_table;     // ... and the copy on the device (the async copy's source lives here)
+        const uint64_t* cur = nullptr;     // the current collect call's bitset, ANDed with the call's accept bits
+    };
+    std::vector<BoolOwner> bools;
+    std::vector<char> filter_bool;             // per clause: its owner is in bool form
+    std::vector<std::vector<int64_t>> filter_terms;  // owned copies of TERMS values
+    // HIP events around the last doc-bitset pass (the bool kernel, or set_preds' fold of more than kMaxPreds clauses),
+    // created on first use, and the bytes it moved (esgpu_plan_last_doc_bitset_stats)
+    hipEvent_t ev_b0 = nullptr, ev_b1 = nullptr;
+    bool bits_timed = false;
+    uint64_t bits_bytes = 0;
+    uint32_t seg_seq = 0;             // segments collected since create / reset (cardinality insertion order)
     uint64_t docs_seen = 0;            // max_doc summed over those segments (u32 terms counts need it below 2^32)
     std::vector<PinnedBuf> h_compact;  // build: per bucket child, its GPU-compacted buckets and leaves (pinned)
     // breadth-first replay: the segments collected while a pipeline was deferred (pinned until reset / destroy) with a
     // device copy of each one's accept bits, and the outer ordinal -> winner slot map of the replay being run
-    struct DeferredSeg { const esgpu_segment* s; int accept; };
+    struct DeferredSeg {
+        const esgpu_segment* s;
+        int accept;                 // d_daccept slot of the query-level doc bitset, -1 = none
+        std::vector<int> baccept;   // parallel to `bools`: the slot of a bool-form filter aggregation's bitset, else -1
+    };
     std::vector<DeferredSeg> dsegs;
     std::vector<DevBuf> d_daccept;
     Scratch s_slotmap;
@@ -1716,8 +1741,16 @@ extern "C" int esgpu_plan_create(esgpu_ctx* c, const esgpu_agg_spec* specs, int3
         }
         p->filter_lo.resize(nfilters);
         p->filter_hi.resize(nfilters);
+        p->filter_terms.resize(nfilters);
         for (int k = 0; k < nfilters; ++k) {
-            require(filters[k].field != nullptr, ESGPU_ERR_INVALID, "filter without field");
+            const bool options = filters[k].type == ESGPU_FILTER_BOOL;  // an owner's options record: no field
+            require(options || filters[k].field != nullptr, ESGPU_ERR_INVALID, "filter without field");
+            require(filters[k].occur >= ESGPU_OCCUR_MUST && filters[k].occur <= ESGPU_OCCUR_MUST_NOT && filters[k].group >= 0,
+                    ESGPU_ERR_INVALID, "filter clause with an unknown occur or a negative group");
+            if (filters[k].type == ESGPU_FILTER_TERMS && filters[k].n_terms > 0) {
+                require(filters[k].terms != nullptr, ESGPU_ERR_INVALID, "terms clause without its values");
+                p->filter_terms[k].assign(filters[k].terms, filters[k].terms + filters[k].n_terms);
+            }
             const int owner = filters[k].owner - 1;  // 0 = query clause, k + 1 = clause of filter aggregation spec k
             require(owner >= -1 && owner < nspecs &&
                         (owner < 0 || p->specs[owner].s.type == ESGPU_AGG_FILTER || p->specs[owner].s.type == ESGPU_AGG_FILTERS),
@@ -1726,12 +1759,63 @@ extern "C" int esgpu_plan_create(esgpu_ctx* c, const esgpu_agg_spec* specs, int3
                 require(filters[k].slot >= 0 && filters[k].slot < p->specs[owner].n_filters, ESGPU_ERR_INVALID,
                         "filter clause slot is not a filter of its filters aggregation");
             p->filters.push_back(filters[k]);
-            p->filter_fields.push_back(filters[k].field);
+            p->filter_fields.push_back(filters[k].field ? filters[k].field : "");
             p->filter_owner.push_back(owner);
             esgpu_filter& f = p->filters.back();
             if (f.lo_term) { p->filter_lo[k].assign((const char*)f.lo_term, (size_t)f.lo_term_len); f.lo_term = (const uint8_t*)p->filter_lo[k].data(); }
             if (f.hi_term) { p->filter_hi[k].assign((const char*)f.hi_term, (size_t)f.hi_term_len); f.hi_term = (const uint8_t*)p->filter_hi[k].data(); }
             f.field = nullptr;  // filter_fields[k] holds it
+            f.terms = nullptr;  // filter_terms[k] holds them
+        }
+        // the owners in bool form: a clause that is not a plain MUST term / range, or an options record
+        p->filter_bool.assign(nfilters, 0);
+        for (int k = 0; k < nfilters; ++k) {
+            const esgpu_filter& f = p->filters[k];
+            if (f.type < ESGPU_FILTER_TERMS && f.occur == ESGPU_OCCUR_MUST && f.group == 0) continue;
+            const int owner = p->filter_owner[k];
+            if (std::any_of(p->bools.begin(), p->bools.end(), [&](const esgpu_plan::BoolOwner& b) { return b.owner == owner; })) continue;
+            if (owner >= 0) {
+                const SpecNode& on = p->specs[owner];
+                require(on.s.type != ESGPU_AGG_FILTERS, ESGPU_ERR_UNSUPPORTED,
+                        "a bool query in a filter of a filters aggregation runs on the CPU path [" + on.name + "]");
+                require(on.s.parent < 0, ESGPU_ERR_UNSUPPORTED,
+                        "a bool query in a filter aggregation below the top level runs on the CPU path [" + on.name + "]");
+            }
+            p->bools.emplace_back();
+            p->bools.back().owner = owner;
+        }
+        for (esgpu_plan::BoolOwner& b : p->bools) {
+            int64_t msm = -1;
+            bool adjust = true, options = false;
+            std::map<std::pair<int, int>, size_t> groups;  // (group, occur) -> clause
+            std::map<int, int> group_occur;
+            for (int k = 0; k < nfilters; ++k) {
+                if (p->filter_owner[k] != b.owner) continue;
+                p->filter_bool[k] = 1;
+                const esgpu_filter& f = p->filters[k];
+                if (f.type == ESGPU_FILTER_BOOL) {
+                    require(!options, ESGPU_ERR_INVALID, "two bool query option records for one owner");
+                    options = true;
+                    msm = f.term;
+                    adjust = f.include_lower != 0;
+                    continue;
+                }
+                if (f.group > 0) {
+                    auto it = group_occur.emplace(f.group, f.occur).first;
+                    require(it->second == f.occur, ESGPU_ERR_INVALID, "the leaves of a bool query group disagree on occur");
+                }
+                const size_t leaf = b.leaves.size();
+                b.leaves.push_back(k);
+                if (leaf >= kBoolLeaves) continue;  // refused at the first collect
+                auto at = f.group > 0 ? groups.find({f.group, f.occur}) : groups.end();
+                if (at == groups.end()) {
+                    if (f.group > 0) groups[{f.group, f.occur}] = b.clauses.size();
+                    b.clauses.push_back({1ull << leaf, f.occur});
+                } else {
+                    b.clauses[at->second].leaves |= 1ull << leaf;
+                }
+            }
+            if (b.leaves.size() <= kBoolLeaves) b.comb = make_bool_comb(b.clauses, msm, adjust);
         }
         // every pipeline evaluates the query clauses plus those of its filter aggregation (set_preds folds more than
         // kMaxPreds of them into a doc bitset)
@@ -1973,6 +2057,7 @@ static int64_t build_key_table(esgpu_plan* p, Pipeline& pl, int64_t lo, int64_t 
 // a clause applies to a pipeline when it is a query clause or belongs to a filter aggregation enclosing the pipeline's
 // (its own filter, and every filter aggregation above it: nested filters intersect, FilterAggregator.java:57-70 per level)
 static bool applies(const esgpu_plan* p, const Pipeline& pl, size_t k) {
+    if (p->filter_bool[k]) return false;  // an owner in bool form: its doc bitset is the pipeline's accept bits (bool_accept)
     const int owner = p->filter_owner[k];
     if (owner < 0) return true;
     for (int x = pl.fspec; x >= 0; x = p->specs[x].s.parent)
@@ -2026,6 +2111,120 @@ static KeyInterval ord_range_interval(const DevColumn* col, const esgpu_filter& 
     });
 }
 
+// HIP events around a doc-bitset pass (esgpu_plan_last_doc_bitset_stats), created on first use
+static void bits_events(esgpu_plan* p) {
+    if (p->ev_b0) return;
+    HIPX(hipEventCreate(&p->ev_b0));
+    HIPX(hipEventCreate(&p->ev_b1));
+}
+
+// The doc bitset of one owner in bool form over one segment (esgpu_bool_bits.hip), ANDed with `accept`: every leaf becomes
+// a union of key intervals on its column (the normalisation set_preds and the filters collect use), every leaf column a
+// table of cuts and leaf masks (build_leaf_masks), and one kernel evaluates the owner's combinator per doc.  A leaf over
+// a field the segment lacks holds for no doc (Lucene: a field without postings), which is not a refusal.
+static void bool_bits_owner(esgpu_plan* p, esgpu_plan::BoolOwner& b, const esgpu_segment* s, const uint64_t* accept) {
+    require(b.leaves.size() <= kBoolLeaves, ESGPU_ERR_UNSUPPORTED, "a bool query with more than 64 leaves runs on the CPU path");
+    struct LeafCol {
+        const DevColumn* col;
+        std::vector<LeafClause> leaves;
+    };
+    std::vector<LeafCol> lcols;
+    BoolBitsParams P{};
+    for (size_t i = 0; i < b.leaves.size(); ++i) {
+        const int k = b.leaves[i];
+        const esgpu_filter& f = p->filters[k];
+        const DevColumn* col = s->col(p->filter_fields[k].c_str());
+        if (!col) continue;
+        require(!col->multi, ESGPU_ERR_UNSUPPORTED, "a bool query over a multi-valued field runs on the CPU path");
+        require(col->type == ESGPU_COL_ORD_U32 || col->type == ESGPU_COL_I64 || col->type == ESGPU_COL_F64, ESGPU_ERR_UNSUPPORTED,
+                "a bool query over a murmur3 field runs on the CPU path");
+        const bool ord = col->type == ESGPU_COL_ORD_U32, f64 = col->type == ESGPU_COL_F64;
+        auto term_iv = [&](int64_t t) {  // as a term clause handles its term: on a double column the long is cast
+            return f64 ? fm_f64_interval(F64Bounds{(double)t, (double)t, 1, 1}) : KeyInterval{t, t};
+        };
+        LeafClause lc;
+        lc.slot = (int32_t)i;
+        if (f.type == ESGPU_FILTER_EXISTS) {
+            lc.exists = true;
+            lc.ivs.push_back(KeyInterval{INT64_MIN, INT64_MAX});
+        } else if (f.type == ESGPU_FILTER_TERMS) {
+            for (int64_t t : p->filter_terms[k]) lc.ivs.push_back(term_iv(t));
+        } else if (f.type == ESGPU_FILTER_TERM) {
+            lc.ivs.push_back(term_iv(f.term));
+        } else if (ord) {
+            lc.ivs.push_back(ord_range_interval(col, f));
+        } else {
+            lc.ivs.push_back(f64 ? fm_f64_interval(fm_f64_bounds(f)) : fm_long_interval(f));
+        }
+        P.all_mask |= 1ull << i;
+        size_t c = 0;
+        while (c < lcols.size() && lcols[c].col != col) ++c;
+        if (c == lcols.size()) {
+            require(lcols.size() < kFilterCols, ESGPU_ERR_UNSUPPORTED, "a bool query over more than 4 fields runs on the CPU path");
+            lcols.push_back({col, {}});
+        }
+        lcols[c].leaves.push_back(std::move(lc));
+    }
+    std::vector<uint64_t> table(std::max<size_t>(lcols.size(), 1) * kFilterStride, 0);
+    uint64_t bytes = 0;
+    for (size_t c = 0; c < lcols.size(); ++c) {
+        const DevColumn* col = lcols[c].col;
+        const bool ord = col->type == ESGPU_COL_ORD_U32, f64 = col->type == ESGPU_COL_F64;
+        const KeyInterval domain = ord ? kOrdDomain : f64 ? fm_f64_domain() : KeyInterval{INT64_MIN, INT64_MAX};
+        require(build_leaf_masks(lcols[c].leaves, (int32_t)b.leaves.size(), domain, f64, table.data() + c * kFilterStride,
+                                 &P.col[c].n_cuts, &P.ex_mask[c]),
+                ESGPU_ERR_UNSUPPORTED, "a bool query with more than 128 distinct leaf bounds on one field runs on the CPU path");
+        P.col[c].kind = ord ? FCOL_ORD : f64 ? FCOL_F64 : FCOL_I64;
+        // (released upload-width values are rebuilt)
+        P.col[c].v = ord ? col->ords().p : wide_i64(p->ctx, col, s, p->stream);
+        P.col[c].present = col->present.as<uint64_t>();
+        bytes += (ord ? 4ull : 8ull) * s->max_doc;
+    }
+    if (table != b.h_table || !b.table.p) {  // (the same request over the same dictionaries: the tables are on the device already)
+        if (b.table.bytes < (size_t)kFilterCols * kFilterStride * 8) b.table.alloc(p->ctx, (size_t)kFilterCols * kFilterStride * 8);
+        b.h_table = std::move(table);
+        HIPX(hipMemcpyAsync(b.table.p, b.h_table.data(), b.h_table.size() * 8, hipMemcpyHostToDevice, p->stream));
+    }
+    const size_t words = std::max<size_t>(s->n_pad / 64, 1);
+    if (b.bits.bytes < words * 8) b.bits.alloc(p->ctx, words * 8 + words * 2);
+    P.n_cols = (uint32_t)lcols.size();
+    P.n_docs = s->max_doc;
+    P.accept = accept;
+    P.table = b.table.as<uint64_t>();
+    P.out = b.bits.as<uint64_t>();
+    P.comb = b.comb;
+    bits_events(p);
+    HIPX(hipEventRecord(p->ev_b0, p->stream));
+    launch_bool_bits(P, s->n_pad, p->ctx->cus, p->stream);
+    HIPX(hipGetLastError());
+    HIPX(hipEventRecord(p->ev_b1, p->stream));
+    p->bits_timed = true;
+    p->bits_bytes = bytes + (accept ? 2 : 1) * (((uint64_t)s->max_doc + 7) / 8);
+    b.cur = b.bits.as<uint64_t>();
+}
+
+// the accept bits of a pipeline: the bitset of the bool-form filter aggregation enclosing it (computed over the query's),
+// else the query's bitset when the query is in bool form, else the call's accept bits
+static const uint64_t* bool_accept(const esgpu_plan* p, const Pipeline& pl, const uint64_t* d_accept) {
+    const uint64_t* a = d_accept;
+    for (const esgpu_plan::BoolOwner& b : p->bools) {
+        if (b.owner < 0) { a = b.cur; continue; }
+        for (int x = pl.fspec; x >= 0; x = p->specs[x].s.parent)
+            if (x == b.owner) return b.cur;
+    }
+    return a;
+}
+
+// ... and of a replay pipeline over a retained segment: the copies kept at its collect
+static const uint64_t* deferred_accept(const esgpu_plan* p, const esgpu_plan::DeferredSeg& d, const Pipeline& pl) {
+    for (size_t i = 0; i < p->bools.size() && i < d.baccept.size(); ++i) {
+        if (d.baccept[i] < 0) continue;
+        for (int x = pl.fspec; x >= 0; x = p->specs[x].s.parent)
+            if (x == p->bools[i].owner) return p->d_daccept[d.baccept[i]].as<uint64_t>();
+    }
+    return d.accept >= 0 ? p->d_daccept[d.accept].as<uint64_t>() : nullptr;
+}
+
 // The pipeline's clauses as device predicates: up to kMaxPreds of them are evaluated inside the collect kernels; with
 // more, all of them (and the accept bitset) are folded first into one doc bitset -- chained filter_bits passes of four
 // clauses each -- which replaces *accept, and no predicate is left for the kernel.
@@ -2033,6 +2232,7 @@ static void set_preds(esgpu_plan* p, const Pipeline& pl, const esgpu_segment* s,
                       uint64_t* bytes_per_doc, const uint64_t** accept) {
     std::vector<PredDev> all;
     *npred = 0;
+    const uint64_t bpd0 = *bytes_per_doc;
     for (size_t k = 0; k < p->filters.size(); ++k) {
         if (!applies(p, pl, k)) continue;
         const esgpu_filter& f = p->filters[k];
@@ -2094,11 +2294,17 @@ static void set_preds(esgpu_plan* p, const Pipeline& pl, const esgpu_segment* s,
     }
     uint64_t* bits = (uint64_t*)p->s_xbits.ensure(p->ctx, std::max<size_t>(s->n_pad / 64, 1) * 8);
     const uint64_t* in = *accept;
+    bits_events(p);
+    HIPX(hipEventRecord(p->ev_b0, p->stream));
+    p->bits_bytes = (*bytes_per_doc - bpd0) * s->max_doc;  // (the pipeline's clause columns at the widths read)
     for (size_t k = 0; k < all.size(); k += kMaxPreds) {
         launch_filter_bits(s->max_doc, in, all.data() + k, (int)std::min<size_t>(kMaxPreds, all.size() - k), bits, p->stream);
         HIPX(hipGetLastError());
+        p->bits_bytes += (in ? 2 : 1) * (((uint64_t)s->max_doc + 7) / 8);
         in = bits;  // in place: each thread reads and rewrites its own word
     }
+    HIPX(hipEventRecord(p->ev_b1, p->stream));
+    p->bits_timed = true;
     *accept = bits;
     *bytes_per_doc += 0;  // the clause columns were counted above; the bitset the kernel then reads is 1 bit per doc
 }
@@ -5177,10 +5383,26 @@ extern "C" int esgpu_plan_collect_segment(esgpu_plan* p, const esgpu_segment* s,
         p->last_ms = -1;
         p->last_kernel = 0;
         p->zu_n = 0;
+        p->bits_timed = false;
+        p->bits_bytes = 0;
+        // owners in bool form: each one's doc bitset once for this segment, whatever the number of its pipelines -- the
+        // query's over the call's accept bits, a filter aggregation's over the query's (the owners are sorted: query first)
+        if (!p->bools.empty()) {
+            std::sort(p->bools.begin(), p->bools.end(),
+                      [](const esgpu_plan::BoolOwner& a, const esgpu_plan::BoolOwner& b) { return a.owner < b.owner; });
+            for (esgpu_plan::BoolOwner& b : p->bools) b.cur = nullptr;
+            const uint64_t* q_accept = d_accept;
+            for (esgpu_plan::BoolOwner& b : p->bools) {
+                bool_bits_owner(p, b, s, q_accept);
+                if (b.owner < 0) q_accept = b.cur;
+            }
+            if (q_accept != d_accept) p->sparse_dead = false;  // (the sample was of the call's bits, not of the query's)
+        }
         bool deferred = false, ranked = false;
         for (Pipeline& pl : p->pipes) {
             if (pl.replay) { pl.timed = false; continue; }
-            pl.timed = pl.kind == 1 ? collect_hll(p, pl, s, d_accept) : collect_grid(p, pl, s, d_accept);
+            const uint64_t* acc = p->bools.empty() ? d_accept : bool_accept(p, pl, d_accept);
+            pl.timed = pl.kind == 1 ? collect_hll(p, pl, s, acc) : collect_grid(p, pl, s, acc);
             deferred |= pl.timed && pl.deferred;
             ranked |= pl.kind != 1 && pl.ranked_live;
         }
@@ -5189,19 +5411,24 @@ extern "C" int esgpu_plan_collect_segment(esgpu_plan* p, const esgpu_segment* s,
             p->dsegs.push_back(esgpu_plan::DeferredSeg{s, -1});
         }
         if (deferred) {  // BestBucketsDeferringCollector: the segment (and its accept bits) kept for the replay at build
-            esgpu_plan::DeferredSeg d{s, -1};
-            if (d_accept) {
-                const size_t bytes = std::max<size_t>(s->n_pad / 64, 1) * 8;
+            esgpu_plan::DeferredSeg d{s, -1, {}};
+            const size_t bytes = std::max<size_t>(s->n_pad / 64, 1) * 8;
+            auto keep = [&](const uint64_t* src) {  // a copy of a doc bitset in a buffer no retained segment uses
                 size_t slot = 0;
-                while (slot < p->d_daccept.size() && std::any_of(p->dsegs.begin(), p->dsegs.end(),
-                                                                 [&](const esgpu_plan::DeferredSeg& x) { return x.accept == (int)slot; }))
-                    ++slot;
+                auto used = [&](const esgpu_plan::DeferredSeg& x) {
+                    return x.accept == (int)slot || std::find(x.baccept.begin(), x.baccept.end(), (int)slot) != x.baccept.end();
+                };
+                while (slot < p->d_daccept.size() && (used(d) || std::any_of(p->dsegs.begin(), p->dsegs.end(), used))) ++slot;
                 if (slot == p->d_daccept.size()) p->d_daccept.emplace_back();
                 DevBuf& b = p->d_daccept[slot];
                 if (b.bytes < bytes) b.alloc(p->ctx, bytes);
-                HIPX(hipMemcpyAsync(b.p, d_accept, bytes, hipMemcpyDeviceToDevice, p->stream));
-                d.accept = (int)slot;
-            }
+                HIPX(hipMemcpyAsync(b.p, src, bytes, hipMemcpyDeviceToDevice, p->stream));
+                return (int)slot;
+            };
+            // the query's bitset (the call's accept bits, or the bool query's over them) and each bool filter aggregation's
+            const uint64_t* q_accept = !p->bools.empty() && p->bools[0].owner < 0 ? p->bools[0].cur : d_accept;
+            if (q_accept) d.accept = keep(q_accept);
+            for (const esgpu_plan::BoolOwner& b : p->bools) d.baccept.push_back(b.owner >= 0 && b.cur ? keep(b.cur) : -1);
             pin_segment(s);
             p->dsegs.push_back(d);
         }
@@ -5257,6 +5484,19 @@ static void resolve_collect_stats(esgpu_plan* p) {
             p->zu_n = 0;
         }
     }
+}
+
+extern "C" int esgpu_plan_last_doc_bitset_stats(const esgpu_plan* p, double* kernel_ms, uint64_t* bytes) {
+    return guarded([&] {
+        require(p != nullptr, ESGPU_ERR_INVALID, "null argument");
+        float ms = 0;
+        if (p->bits_timed) {
+            HIPX(hipEventSynchronize(p->ev_b1));
+            HIPX(hipEventElapsedTime(&ms, p->ev_b0, p->ev_b1));
+        }
+        if (kernel_ms) *kernel_ms = p->bits_timed ? (double)ms : -1.0;
+        if (bytes) *bytes = p->bits_timed ? p->bits_bytes : 0;
+    });
 }
 
 extern "C" int esgpu_plan_last_collect_stats(const esgpu_plan* cp, double* kernel_ms, uint64_t* bytes, int32_t* path) {
@@ -5915,8 +6155,8 @@ static bool replay_pass(esgpu_plan* p, const ChildSrc& kid, const std::vector<Te
             R.fresh = true;
         }
         for (const esgpu_plan::DeferredSeg& d : p->dsegs) {
-            const uint64_t* acc = d.accept >= 0 ? p->d_daccept[d.accept].as<uint64_t>() : nullptr;
             for (size_t j = 0; j < kid.rpipes.size(); ++j) {
+                const uint64_t* acc = deferred_accept(p, d, p->pipes[kid.rpipes[j]]);
                 const bool done = collect_grid(p, p->pipes[kid.rpipes[j]], d.s, acc);
                 if (j == 0) any |= done;
             }
@@ -6012,7 +6252,7 @@ static bool replay_compact(esgpu_plan* p, const ChildSrc& kid, const std::vector
         C.wb = wb;
         C.stride = (uint32_t)stride;
         C.nbatch = nbatch;
-        const uint64_t* acc = d.accept >= 0 ? p->d_daccept[d.accept].as<uint64_t>() : nullptr;
+        const uint64_t* acc = deferred_accept(p, d, R0);
         uint64_t bytes = 0;
         set_preds(p, R0, d.s, C.pred, &C.npred, &bytes, &acc);
         C.accept = acc;
@@ -6068,7 +6308,7 @@ static bool replay_hot(esgpu_plan* p, const ChildSrc& kid, const std::vector<Ter
     if (Hh < kk || kk > kTopkMax) return false;
     const uint64_t bound = Hh < hs->hot_n ? (uint64_t)hs->hot_cnt[Hh] : hs->max_cold;
     // the request's clauses (as the collect applied them) and live docs, folded into one bitset
-    const uint64_t* acc = d.accept >= 0 ? p->d_daccept[d.accept].as<uint64_t>() : nullptr;
+    const uint64_t* acc = deferred_accept(p, d, R0);
     PredDev pred[4];
     int32_t npred = 0;
     uint64_t bytes = 0;
@@ -7279,6 +7519,8 @@ extern "C" int esgpu_plan_destroy(esgpu_plan* p) {
         }
         p->pipes.clear();
         if (p->ev_mid) (void)hipEventDestroy(p->ev_mid);
+        if (p->ev_b0) (void)hipEventDestroy(p->ev_b0);
+        if (p->ev_b1) (void)hipEventDestroy(p->ev_b1);
         if (p->ev_xr) (void)hipEventDestroy(p->ev_xr);
         if (p->ev0) (void)hipEventDestroy(p->ev0);
         if (p->ev1) (void)hipEventDestroy(p->ev1);

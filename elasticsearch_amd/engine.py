@@ -230,6 +230,13 @@ class Plan:
         N.check(N.lib().esgpu_plan_last_collect_stats(self._ptr, ctypes.byref(ms), ctypes.byref(nbytes), ctypes.byref(path)))
         return ms.value, nbytes.value, path.value
 
+    def last_doc_bitset_stats(self):
+        """(kernel_ms, bytes) of the last collect's doc-bitset pass -- a bool query's kernel, or the fold of more than
+        four plain clauses; (-1.0, 0) when the collect made none"""
+        ms, nbytes = ctypes.c_double(), ctypes.c_uint64()
+        N.check(N.lib().esgpu_plan_last_doc_bitset_stats(self._ptr, ctypes.byref(ms), ctypes.byref(nbytes)))
+        return ms.value, nbytes.value
+
     def last_collect_kernel(self):
         """0: the generic collect kernel ran the last collect, 1: the ranked kernel"""
         kid = ctypes.c_int32()

@@ -401,13 +401,46 @@ enum {
     ESGPU_FORMAT_NUMBER = 2       /* ValueFormatter.Number.Pattern, stream id 4 (pattern) */
 };
 
-/* Query filters: bool{filter:[...]} conjunction of term / range clauses. */
+/* Query filters.  The clauses of one owner (esgpu_filter.owner) are a bool query.
+ *
+ * Plain form -- every clause ESGPU_FILTER_TERM or ESGPU_FILTER_RANGE with occur ESGPU_OCCUR_MUST and group 0, and no
+ * ESGPU_FILTER_BOOL record -- is bool{filter:[...]}, the conjunction of the clauses; a zero-initialised tail of the
+ * struct means exactly that.  It is evaluated inside the collect kernels (more than four clauses: folded into a doc
+ * bitset first) and accepts multi-valued and ESGPU_COL_U64 columns.
+ *
+ * Anything else is bool form (BoolQueryBuilder.doToQuery, index/query/BoolQueryBuilder.java:264-277; Queries
+ * .applyMinimumShouldMatch / fixNegativeQueryIfNeeded, common/lucene/search/Queries.java:87-136).  The owner's clauses
+ * are its leaves with group 0, each a clause by itself, and its groups: the leaves with the same group > 0 (and the same
+ * occur) form one clause that holds when any of them holds -- a nested bool of should leaves.  A doc matches iff every
+ * ESGPU_OCCUR_MUST clause holds (must and filter alike: nothing is scored), no ESGPU_OCCUR_MUST_NOT clause holds and at
+ * least m ESGPU_OCCUR_SHOULD clauses hold; m = the BOOL record's minimum_should_match when that is > 0, else 1 when the
+ * owner has no MUST clause and at least one SHOULD clause, else 0.  No clause at all is match_all; only MUST_NOT clauses
+ * match every doc none of them holds for when adjust_pure_negative, else no doc.  A leaf over a field the segment lacks
+ * holds for no doc of it.  The owner's doc set is computed once per segment per collect call as a doc bitset by one
+ * kernel over the distinct leaf columns (DESIGN.md §5 "Bool queries") and handed to every collect path as its accept
+ * bits, ANDed with the caller's.
+ * Bool form is built for owner 0 (the request query) and for a top-level ESGPU_AGG_FILTER; for a slot of an
+ * ESGPU_AGG_FILTERS and for a filter aggregation that is not top level esgpu_plan_create returns ESGPU_ERR_UNSUPPORTED
+ * ("bool query ...").  ESGPU_ERR_UNSUPPORTED at the first collect that shows it: more than 64 leaves in one owner, more
+ * than 4 distinct leaf columns, more than 128 distinct cuts (leaf bounds) on one column, a multi-valued or
+ * ESGPU_COL_U64 leaf column.  ESGPU_ERR_INVALID at esgpu_plan_create: a group whose leaves disagree on occur, two BOOL
+ * records for one owner, TERMS with n_terms > 0 and a null pointer. */
 enum {
     ESGPU_FILTER_TERM = 1,        /* doc matches if any value == term (numeric: TermQuery on the prefix-coded long;
                                      keyword: the term's ordinal; -1 = term not in dictionary => no match) */
-    ESGPU_FILTER_RANGE = 2        /* doc matches if any value in [lo,hi] with include flags (NumericRangeQuery; on a
+    ESGPU_FILTER_RANGE = 2,       /* doc matches if any value in [lo,hi] with include flags (NumericRangeQuery; on a
                                      keyword field TermRangeQuery over the term bytes lo_term / hi_term) */
+    ESGPU_FILTER_TERMS = 3,       /* TermsQueryBuilder: the doc's value is one of terms[0 .. n_terms), each handled as TERM
+                                     handles its term (keyword: ordinals, -1 matches nothing; a double column: the long
+                                     cast); n_terms == 0 matches no doc.  Bool form. */
+    ESGPU_FILTER_EXISTS = 4,      /* ExistsQueryBuilder: the doc has a value in the field -- a set present bit, an ordinal
+                                     other than the missing one; a NaN double is a value.  Bool form. */
+    ESGPU_FILTER_BOOL = 5         /* the owner's options, no leaf (field is not read): term = the resolved
+                                     minimum_should_match (Queries.calculateMinShouldMatch over the owner's SHOULD
+                                     clauses) or -1 when the request gave none, include_lower = adjust_pure_negative.  At
+                                     most one per owner; absent: -1 and true.  Its presence makes the owner bool form. */
 };
+enum { ESGPU_OCCUR_MUST = 0, ESGPU_OCCUR_SHOULD = 1, ESGPU_OCCUR_MUST_NOT = 2 };
 typedef struct esgpu_filter {
     int32_t type;
     int32_t include_lower;
@@ -428,6 +461,11 @@ typedef struct esgpu_filter {
     int32_t slot;                 /* a clause whose owner is an ESGPU_AGG_FILTERS spec: the filter of that spec it belongs
                                      to (index into filter_keys); 0 otherwise */
     int32_t reserved_slot;
+    int32_t occur;                /* ESGPU_OCCUR_*: 0 = MUST (must and filter alike) */
+    int32_t group;                /* 0 = the leaf is a clause by itself; g > 0 = the leaves of one owner with this group
+                                     and occur form one clause that holds when any of them holds */
+    const int64_t* terms;         /* TERMS: the values (copied by esgpu_plan_create) */
+    uint64_t n_terms;
 } esgpu_filter;
 
 int esgpu_terms_thresholds(int32_t size, int32_t shard_size, int64_t min_doc_count, int64_t shard_min_doc_count,
@@ -505,6 +543,12 @@ int esgpu_plan_destroy(esgpu_plan* plan);
  * its key range). */
 int esgpu_plan_last_collect_stats(const esgpu_plan* plan, double* kernel_ms, uint64_t* algorithmic_bytes,
                                   int32_t* path);
+/* The last collect_segment's doc-bitset pass, which esgpu_plan_last_collect_stats does not count: the bool kernel of an
+ * owner in bool form (the last owner's, when a request has several), or the chained fold of a plain owner's more than
+ * four clauses (the last pipeline's).  kernel_ms: HIP events on the plan's stream (synchronises with it); bytes: the
+ * clause columns at the widths read, the accept bits read and the bitset written, 1/8 byte per doc each (the fold: per
+ * pass of four clauses).  -1 ms and 0 bytes when the collect made no such pass. */
+int esgpu_plan_last_doc_bitset_stats(const esgpu_plan* plan, double* kernel_ms, uint64_t* bytes);
 /* The kernel that ran the last collect's LDS-window launch: 0 the generic collect kernel, 1 the ranked kernel (path 10
  * where ESGPU_OPT_RANKED_TERMS = 1, 3, 4 or 5 and the shape allows), 2 its grouped form (ESGPU_OPT_RANKED_TERMS = 5). */
 int esgpu_plan_last_collect_kernel(const esgpu_plan* plan, int32_t* id);
