@@ -1,7 +1,8 @@
 // group12_check.cpp — the g12 layout of es_group12.hpp on the host, under AddressSanitizer + UBSan (make check-group12):
 // the reference grouping of a block and the position-to-rank lookup against brute force -- every position's delta is a
 // delta of a doc of the rank the lookup names, as a multiset per rank; the offsets are the counts of the lower groups;
-// the lookup of 8 positions agrees with the lookup of one; the prefix byte counts.  Stand-alone, no GPU.
+// the lookup of 8 positions agrees with the lookup of one; the prefix byte counts; the group a lane of the grouped kernel
+// loads for every prefix and position (g12_load_group: its own or group 0, inside the block).  Stand-alone, no GPU.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -115,6 +116,29 @@ int main() {
               g12_prefix_bytes(kG12Block) == g12_block_bytes() && g12_block_bytes() == 12288,
           "prefix bytes");
     CHECK(kG12OffBytes == 260 && kG12OffBytes % 4 == 0, "offset stride");
+    // the group a lane of the grouped kernel loads (g12_load_group), for every prefix n and every p0 a thread holds: its
+    // own group, which then lies below ceil8(n), or group 0 -- and its 12 bytes inside the block's data, read here from
+    // a tight heap block
+    {
+        std::vector<uint8_t> data(g12_block_bytes(), 1);
+        uint64_t own = 0, clamped = 0, sum = 0;
+        for (uint32_t n = 0; n <= kG12Block; ++n) {
+            for (uint32_t p0 = 0; p0 < kG12Block; p0 += kP12Group) {
+                const uint32_t g = g12_load_group(p0, n);
+                const size_t byte = (size_t)g * (kP12Words * 4);
+                const bool is_own = g == p0 / kP12Group && (uint64_t)g * kP12Group < g12_ceil8(n);
+                CHECK(is_own || g == 0, "load group: n %u p0 %u -> group %u", n, p0, g);
+                CHECK(is_own == (p0 < n) || (g == 0 && p0 == 0), "load group: n %u p0 %u own %d", n, p0, (int)is_own);
+                CHECK(byte + kP12Words * 4 <= g12_block_bytes() && byte + kP12Words * 4 <= std::max<size_t>(g12_prefix_bytes(n), kP12Words * 4),
+                      "load group: n %u p0 %u reads bytes [%zu, +12)", n, p0, byte);
+                for (uint32_t i = 0; i < kP12Words * 4; ++i) sum += data[byte + i];
+                ++(is_own ? own : clamped);
+            }
+        }
+        CHECK(sum == (own + clamped) * kP12Words * 4, "load group: bytes read");
+        std::printf("group12_check: load group over n = 0..%u: %llu own, %llu clamped to group 0\n", kG12Block, (unsigned long long)own,
+                    (unsigned long long)clamped);
+    }
     if (failures) {
         std::fprintf(stderr, "group12_check: %d failures\n", failures);
         return 1;

@@ -32,6 +32,11 @@ ES_P12_HD size_t g12_data_bytes(size_t n_blocks) { return n_blocks * g12_block_b
 ES_P12_HD size_t g12_off_bytes(size_t n_blocks) { return n_blocks * kG12OffBytes; }
 // bytes of a block's data a collect of the ranks below K streams: the groups of 8 that hold positions below n = off[K]
 ES_P12_HD size_t g12_prefix_bytes(uint64_t n) { return p12_bytes((size_t)g12_ceil8(n)); }
+// the group of 8 a thread that holds the positions p0 .. p0 + 7 (p0 a multiple of 8, < kG12Block) loads from a block
+// with n = off[K]: its own where that holds a collected position, otherwise group 0 -- always inside the block's data,
+// and re-read by the thread that owns it (the grouped kernel's loads are unconditional; what such a thread gets it
+// ignores).  The byte offset inside the block is kP12Words * 4 times this.
+ES_P12_HD uint32_t g12_load_group(uint32_t p0, uint32_t n) { return p0 < n ? p0 / kP12Group : 0u; }
 
 // the rank of position p for a collect of the ranks below K (K <= kG12Groups): off(j) gives the block's off[j]
 template <class OffAt>

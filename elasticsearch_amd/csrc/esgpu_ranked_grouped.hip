@@ -10,14 +10,20 @@
 //     included (its pad docs are in the group nothing collects);
 //   - any other block (several keys, a key outside the grid) takes the per-doc body over the original, unpermuted
 //     columns -- rank16, d16 and the block-delta keys -- loaded there.
-// A block's prefix (both passes of 512 threads x 8 positions) is prefetched two blocks ahead into one of two buffers
-// (even and odd blocks), with the block's offsets off[1..K], one per lane.  The offsets are uniform over the wave and
-// never searched in memory: two ballots over them give a wave the rank of its first position and the number of
-// offsets below its last, and a thread counts the ranks of its positions (g12_ranks8) over the offsets between the two,
-// read from their lanes.  The zone keys and n = off[K] are scalar loads issued a further two blocks ahead, so that the
-// prefetch of a block knows which lanes have something to load.  ESGPU_OPT_RANKED_TERMS = 5 takes this kernel up to 16
-// ranks: with many offsets inside a wave's positions the rank count and the walk of the runs cost more than the
-// per-doc body they replace.
+// The unit of work is a (block, pass) pair: a pass is 512 threads x 8 positions, so a block with n <= 4096 -- nearly
+// every block of a request for a few ranks -- is one unit, a block with more two.  Four units are in flight per
+// workgroup, in a ring of four slots (rg_slot): the thread's group of 8 of the unit, and the block's offsets off[1..K],
+// one per lane.  A slot is refilled for the unit four ahead right after its unit is processed.  Every lane issues every
+// load of every unit, in one order (rk_pin keeps it): a lane with nothing to read loads a clamped address
+// (g12_load_group; off[K] for the offsets; the range's last block past its end) and ignores what it got, so the waits
+// are counted -- a unit is entered with the three younger slots' loads outstanding.  The offsets are uniform over the
+// wave and never searched in memory: two ballots over them give a wave the rank of its first position and the number
+// of offsets below its last, and a thread counts the ranks of its positions (g12_ranks8) over the offsets between the
+// two, read from their lanes.  The blocks' scalars -- n = off[K] and the block's one key -- are held one block per lane
+// for up to 64 blocks (a chunk of the range) from two vector loads in front of the chunk, so the sequence of units,
+// which depends on the n alone, is known where a slot is refilled, and the loop has no scalar load to wait for.
+// ESGPU_OPT_RANKED_TERMS = 5 takes this kernel up to 16 ranks: with many offsets inside a wave's positions the rank
+// count and the walk of the runs cost more than the per-doc body they replace.
 #include "es_group12.hpp"
 #include "esgpu_ranked_cells.hpp"
 
@@ -30,18 +36,23 @@ constexpr uint32_t kRgPass = kRkWG * kP12Group;  // positions a workgroup covers
 static_assert(kG12Block == kBlockDocs && kBlockDocs == 2 * kRgPass, "a g12 block is a zone block: two passes of a workgroup");
 static_assert(kG12Groups == 2 * 64, "a block's offsets off[1..K] are two registers of a wave");
 
-typedef const uint32_t __attribute__((address_space(4))) rg_word_c;
+constexpr uint32_t kRgOther = 0xFFFFFFFFu;  // (no key: the grid has fewer than 2^32 - 1)
+constexpr uint32_t kRgChunk = 64;           // blocks whose scalars a wave holds, one per lane
 
-// one block's prefetch: the thread's group of 8 positions of each of the block's two passes, and the wave's copy of the
-// offsets -- lane l holds off[1 + l] in o0 and off[65 + l] in o1 (those up to off[K]; 0xFFFF past them)
-struct rg_buf {
-    u32x3_t v[kBlockDocs / kRgPass];  // the thread's group of each pass
+// one slot of the ring: a unit, its scalars, the thread's group of 8 positions of the unit's pass, and the wave's copy
+// of the block's offsets -- lane l loaded off[1 + l] into o0 and off[65 + l] into o1 (a lane past K: off[K], which the
+// uses replace by 0xFFFF -- never a copy made where it is loaded)
+struct rg_slot {
+    uint32_t u;   // 2 * block + pass; a block at or past the range's end: nothing to process
+    uint32_t n;   // the block's off[K]
+    uint32_t key; // the block's one key inside the grid, or kRgOther: several keys, or one outside the grid
+    u32x3_t v;
     uint32_t o0, o1;
 };
 
-__device__ __forceinline__ u32x3_t rg_load(const uint8_t* g12, uint32_t blk, uint32_t p0) {  // p0: a multiple of 8, < off[K]
+__device__ __forceinline__ u32x3_t rg_load(const uint8_t* g12, uint32_t blk, uint32_t p0, uint32_t n) {  // p0: a multiple of 8
     return __builtin_nontemporal_load(
-        reinterpret_cast<const u32x3_a4_t*>(g12 + (size_t)blk * g12_block_bytes() + (p0 / kP12Group) * (kP12Words * 4)));
+        reinterpret_cast<const u32x3_a4_t*>(g12 + (size_t)blk * g12_block_bytes() + g12_load_group(p0, n) * (kP12Words * 4)));
 }
 
 // one run of a thread's positions into its cell: the packed add of the run's sum and count, and the bounds -- READ:
@@ -138,98 +149,119 @@ __global__ __launch_bounds__(kRkWG, ESGPU_RG_WAVES) void ranked_grouped_kernel(R
     };
 
     const zkey_pair_c* const zk = zkey_view(P.zkey);
-    rg_word_c* const offw = (rg_word_c*)P.g12_off;
     const uint8_t* const g12 = (const uint8_t*)P.g12;
     const uint32_t lane = threadIdx.x & 63u, tid8 = threadIdx.x * kP12Group;
     const uint32_t wave0 = __builtin_amdgcn_readfirstlane(tid8 & ~(64u * kP12Group - 1u));  // the wave's first position of a pass
-    const uint32_t last = b_end - 1;
-    // (past the range's end the scalar loads read the last block's again: the values are not used)
-    auto zload = [&](uint32_t b) -> i64x2_t { return zk[__builtin_amdgcn_readfirstlane(min(b, last))]; };
-    auto nload = [&](uint32_t b) -> uint32_t {  // off[K] of block b: one half of a word
-        const uint32_t i = __builtin_amdgcn_readfirstlane(min(b, last)) * kG12OffStride + K;
-        const uint32_t w = offw[i >> 1];
-        return (i & 1u) ? w >> 16 : w & 0xFFFFu;
+    // A range is walked in chunks of up to 64 blocks.  The scalars of a chunk's blocks -- n = off[K], and the block's one
+    // key or kRgOther -- are held one block per lane (nv, kv: lane l holds block c0 + l, past the chunk's end its last
+    // block again) from two vector loads in front of the chunk, and read from their lane where a slot is filled: the
+    // loop has no scalar load, whose wait -- scalar loads return out of order, so it is a wait for all of them and
+    // stands in front of every LDS read -- would expose a block's miss in every unit.
+    uint32_t c0 = b_begin, last = b_begin, cu = 0, nv = 0, kv = 0;
+    // fill: every lane loads the unit's group (its own or group 0) and two offsets (its own or off[K]), then the unit
+    // behind it becomes the next; past the chunk's end the last block's again, with n = 0: one unit, nothing to read
+    auto fill = [&](rg_slot& S) {
+        const uint32_t blk = min(cu >> 1, last), q = cu & 1u;
+        const uint32_t n = (cu >> 1) > last ? 0u : (uint32_t)__builtin_amdgcn_readlane((int)nv, (int)(blk - c0));
+        S.u = cu;
+        S.n = n;
+        S.key = (uint32_t)__builtin_amdgcn_readlane((int)kv, (int)(blk - c0));
+        S.v = rg_load(g12, blk, q * kRgPass + tid8, n);
+        const uint16_t* const o = P.g12_off + (size_t)blk * kG12OffStride + 1;
+        S.o0 = o[min(lane, K - 1u)];
+        S.o1 = o[min(lane + 64u, K - 1u)];
+        cu = q == 0 && n > kRgPass ? cu + 1u : (cu | 1u) + 1u;
     };
-    // block blk's prefix (n = its off[K]) and its offsets: only the lanes that have something to load
-    auto prefetch = [&](rg_buf& B, uint32_t blk, uint32_t n) {
-        if (n > 0) {
-#pragma unroll
-            for (uint32_t q = 0; q < kBlockDocs / kRgPass; ++q)
-                if (q * kRgPass + tid8 < n) B.v[q] = rg_load(g12, blk, q * kRgPass + tid8);
-            const uint16_t* const o = P.g12_off + (size_t)blk * kG12OffStride + 1;
-            if (lane < K) B.o0 = o[lane];
-            if (lane + 64u < K) B.o1 = o[lane + 64u];
-        }
-    };
-    auto block = [&](const rg_buf& B, uint32_t blk, i64x2_t z, uint32_t n) {
-        const int64_t kmn = z.x, kmx = z.y;
-        // (every lane reads the same zone keys: the decisions are uniform over the workgroup)
-        const bool any = kmn <= kmx && kmx >= 0 && kmn < (int64_t)P.H;  // some doc of the block may lie in the grid
-        if (any) {
-            const bool fits = kmx - kmn < (int64_t)W;
-            if (!win_set || (fits && (kmn < (int64_t)win0 || kmx >= (int64_t)win0 + (int64_t)W)))
-                slide_to((uint32_t)min(max(kmn, (int64_t)0), (int64_t)P.H - 1));
-        }
-        const bool fast = kmn == kmx && (uint64_t)kmn < (uint64_t)P.H;
-        if (!fast && any) {  // the per-doc body: 16 docs per thread in quads, from the original columns
-            const auto& Q = *rk_again();
+    auto unit = [&](const rg_slot& S) {
+        const uint32_t blk = S.u >> 1, q = S.u & 1u, n = S.n, key = S.key;
+        if (blk > last) return;  // (a unit past the chunk's end: the ring's last refills)
+        const bool fast = key != kRgOther;
+        if (q == 0) {  // the block's own business, once
+            // one key inside the grid fits any window; any other block's keys are read again here
+            int64_t kmn = key, kmx = key;
+            if (!fast) {
+                const i64x2_t z = zk[__builtin_amdgcn_readfirstlane(blk)];
+                kmn = z.x;
+                kmx = z.y;
+            }
+            const bool any = kmn <= kmx && kmx >= 0 && kmn < (int64_t)P.H;  // some doc of the block may lie in the grid
+            if (any) {
+                const bool fits = kmx - kmn < (int64_t)W;
+                if (!win_set || (fits && (kmn < (int64_t)win0 || kmx >= (int64_t)win0 + (int64_t)W)))
+                    slide_to((uint32_t)min(max(kmn, (int64_t)0), (int64_t)P.H - 1));
+            }
+            dirty = dirty || any;
+            if (!fast && any) {  // the per-doc body: 16 docs per thread in quads, from the original columns
+                const auto& Q = *rk_again();
 #pragma unroll 1
-            for (uint32_t q = 0; q < kBlockDocs / (4u * kRkWG); ++q) {
-                const uint32_t doc0 = blk * kBlockDocs + (q * kRkWG + threadIdx.x) * 4u;
-                rk_r4<2> r = {0xFFFFFFFFu, 0xFFFFFFFFu};
-                uint32_t m0 = 0, m1 = 0;
-                if (doc0 < Q.n_docs) {  // (the columns are padded to whole blocks: the quad lies inside them)
-                    const u32x2_t rr = load8((const uint16_t*)Q.rank + doc0), mv = load8((const uint16_t*)Q.mv + doc0);
-                    r = {rr.x, rr.y};
-                    m0 = mv.x;
-                    m1 = mv.y;
+                for (uint32_t i = 0; i < kBlockDocs / (4u * kRkWG); ++i) {
+                    const uint32_t doc0 = blk * kBlockDocs + (i * kRkWG + threadIdx.x) * 4u;
+                    rk_r4<2> r = {0xFFFFFFFFu, 0xFFFFFFFFu};
+                    uint32_t m0 = 0, m1 = 0;
+                    if (doc0 < Q.n_docs) {  // (the columns are padded to whole blocks: the quad lies inside them)
+                        const u32x2_t rr = load8((const uint16_t*)Q.rank + doc0), mv = load8((const uint16_t*)Q.mv + doc0);
+                        r = {rr.x, rr.y};
+                        m0 = mv.x;
+                        m1 = mv.y;
+                    }
+                    rk_slow_quad<MET, 2, 16>(doc0, r, m0, m1, kmn, kmx, K, win0, win_set ? W : 0u, pk, mm, coff, sh);
                 }
-                rk_slow_quad<MET, 2, 16>(doc0, r, m0, m1, kmn, kmx, K, win0, win_set ? W : 0u, pk, mm, coff, sh);
+                rk_drain();  // (its own loads have landed: the join below is not a wait for everything in flight)
             }
         }
-        dirty = dirty || any;
-        if (fast && n > 0) {
-            const uint32_t rowm = cell0 + 8u * (((uint32_t)kmn - win0) * K);
+        if (fast && q * kRgPass < n) {
+            const uint32_t rowm = cell0 + 8u * ((key - win0) * K);
+            // a lane past K holds no offset: above every position
+            const uint32_t o0 = lane < K ? S.o0 : kG12Missing, o1 = lane + 64u < K ? S.o1 : kG12Missing;
             // the wave's span of positions among the offsets: every lane compares its offset, two ballots count them
-            auto span = [&](uint32_t w0, uint32_t& base, uint32_t& upto) {
-                base = (uint32_t)__popcll(__ballot(B.o0 <= w0));
-                upto = (uint32_t)__popcll(__ballot(B.o0 < w0 + 64u * kP12Group));
-                if (K > 64u) {
-                    base += (uint32_t)__popcll(__ballot(B.o1 <= w0));
-                    upto += (uint32_t)__popcll(__ballot(B.o1 < w0 + 64u * kP12Group));
-                }
-            };
-            // (the second pass: more than half of the block's docs collected)
-#pragma unroll
-            for (uint32_t q = 0; q < kBlockDocs / kRgPass; ++q) {
-                if (q * kRgPass < n) {
-                    uint32_t base, upto;
-                    span(q * kRgPass + wave0, base, upto);
-                    rg_group8<MET>(B.v[q], q * kRgPass + tid8, n, K, base, upto, B.o0, B.o1, rowm, dpk, onehi);
-                }
+            const uint32_t w0 = q * kRgPass + wave0;
+            uint32_t base = (uint32_t)__popcll(__ballot(o0 <= w0));
+            uint32_t upto = (uint32_t)__popcll(__ballot(o0 < w0 + 64u * kP12Group));
+            if (K > 64u) {
+                base += (uint32_t)__popcll(__ballot(o1 <= w0));
+                upto += (uint32_t)__popcll(__ballot(o1 < w0 + 64u * kP12Group));
             }
+            // (the offsets read from a lane are off[base + 1 .. upto], upto <= K: lanes that hold one)
+            rg_group8<MET>(S.v, q * kRgPass + tid8, n, K, base, upto, S.o0, S.o1, rowm, dpk, onehi);
         }
     };
 
-    i64x2_t za = zload(b_begin), zb = zload(b_begin + 1);
-    uint32_t na = nload(b_begin), nb = nload(b_begin + 1);
-    rg_buf A = {{{0, 0, 0}, {0, 0, 0}}, kG12Missing, kG12Missing}, B = A;  // (a lane past K holds no offset: above every position)
-    prefetch(A, b_begin, na);
-    rk_pin();
-    if (b_begin + 1 < b_end) prefetch(B, b_begin + 1, nb);
-    rk_pin();
-#pragma unroll 1
-    for (uint32_t cb = b_begin; cb < b_end; cb += 2) {
-        const i64x2_t za2 = zload(cb + 2), zb2 = zload(cb + 3);
-        const uint32_t na2 = nload(cb + 2), nb2 = nload(cb + 3);
-        block(A, cb, za, na);
-        if (cb + 2 < b_end) prefetch(A, cb + 2, na2);
+    for (; c0 < b_end; c0 += kRgChunk) {
+        last = min(c0 + kRgChunk, b_end) - 1u;
+        {  // (every lane of a wave reads its own block's zone keys; what is read back from a lane is uniform over the workgroup)
+            const uint32_t bl = min(c0 + lane, last);
+            const i64x2_t z = *reinterpret_cast<const i64x2_t*>(P.zkey + 2u * (size_t)bl);
+            kv = z.x == z.y && (uint64_t)z.x < (uint64_t)P.H ? (uint32_t)z.x : kRgOther;
+            nv = P.g12_off[(size_t)bl * kG12OffStride + K];
+        }
+        cu = 2u * c0;
+        rg_slot S0, S1, S2, S3;
+        fill(S0);
         rk_pin();
-        if (cb + 1 < b_end) block(B, cb + 1, zb, nb);
-        if (cb + 3 < b_end) prefetch(B, cb + 3, nb2);
+        fill(S1);
         rk_pin();
-        za = za2; zb = zb2;
-        na = na2; nb = nb2;
+        fill(S2);
+        rk_pin();
+        fill(S3);
+        rk_pin();
+        // the loop is unrolled by the ring's depth, so every slot is a register set of its own, and has one exit (an
+        // exit in front of each unit is compiled as a path from every refill to the loop's head, and the first slot is
+        // then entered through vmcnt(0)): the chunk ends in any slot, and the refills behind it load the last block's
+        // group 0 again
+        do {
+            unit(S0);
+            fill(S0);
+            rk_pin();
+            unit(S1);
+            fill(S1);
+            rk_pin();
+            unit(S2);
+            fill(S2);
+            rk_pin();
+            unit(S3);
+            fill(S3);
+            rk_pin();
+        } while ((S0.u >> 1) <= last);
     }
     if (dirty) flush();
 }
