@@ -179,15 +179,20 @@ __global__ __launch_bounds__(kRgWG) void mask_hist_kernel(PARAMS P, HistKeys K) 
         const bool nokey = kmn > kmx;
         const bool single = kmn == kmx && (uint64_t)kmn < (uint64_t)K.H;
         // the window moves to a block whose rows it does not hold (a block of more than kMhSlots rows: to its first ones)
-        if (!nokey && (uint64_t)kmn < (uint64_t)K.H &&
-            (w0 == kNoRow || kmn < (int64_t)w0 || kmx >= (int64_t)w0 + (int64_t)kMhSlots)) {
-            if (w0 != kNoRow) {
-                __syncthreads();
-                mh_flush<MET>(cells, ocnt, P, R, vcnt, w0);
-                __syncthreads();
-            }
-            w0 = (uint32_t)kmn;
+        // (a flag, the flush under it, then a select.  Written as `if (move) { if (w0 != kNoRow) flush; w0 = kmn; }` --
+        // the same program -- hipcc of ROCm 7.2.0 (AMD clang 22.0.0git, roc-7.2.0) at -O3 for gfx950 set the window's
+        // register to kmn only on the path where w0 was unset and kept the old w0 on the path through the flush, in all
+        // eight instantiations: the next single-key block then indexed the cells past their end.  This form compiles to
+        // an s_cselect after the second barrier.  tests/test_gpu_mask_block_carry.py walks that path; with a later
+        // toolchain the plain form may be tried against it again.)
+        const bool move = !nokey && (uint64_t)kmn < (uint64_t)K.H &&
+                          (w0 == kNoRow || kmn < (int64_t)w0 || kmx >= (int64_t)w0 + (int64_t)kMhSlots);
+        if (move && w0 != kNoRow) {
+            __syncthreads();
+            mh_flush<MET>(cells, ocnt, P, R, vcnt, w0);
+            __syncthreads();
         }
+        w0 = move ? (uint32_t)kmn : w0;
         // several keys: the magic division holds while every timestamp of the block is within 2^32 of its first key
         const bool fast = !nokey && kmn >= 0 && K.keys32 != 0 && (uint64_t)(kmx - kmn) < (uint64_t)K.keys32;
         const int64_t vb = (K.key0 + kmn) * K.interval + K.offset;

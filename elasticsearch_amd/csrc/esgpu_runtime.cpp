@@ -3650,6 +3650,9 @@ static void mask_collect_launch(esgpu_plan* p, Pipeline& pl, const esgpu_segment
     }
     const uint32_t slots = std::max(1u, (uint32_t)p->ctx->cus * (uint32_t)pl.occ);
     P.blocks_per_wg = (P.n_blocks + slots - 1) / slots;
+    // tests only: ESGPU_DEBUG_BPW, as at the cell-grid launch (read at each collect; a positive number replaces the
+    // computed value, so that a segment of a few blocks walks the cells' and the key window's block-to-block carry)
+    if (const char* e = std::getenv("ESGPU_DEBUG_BPW"); e && std::atoi(e) > 0) P.blocks_per_wg = (uint32_t)std::atoi(e);
     launch((P.n_blocks + P.blocks_per_wg - 1) / P.blocks_per_wg);
     HIPX(hipGetLastError());
     if (P.g_sum_lo) launch_dd_fold(P.g_sum, P.g_sum_lo, cells, p->stream);
